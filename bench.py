@@ -23,6 +23,14 @@ Scaling modes:
          batch = 64 / N.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+                       [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line.
+  --dump-outputs DIR  write what the last timed step returned (the logits and
+         every loss of ``TrainStep.step``) to DIR/<name>.npy as float32.  Data
+         and initial weights are seeded: the same arguments give the same inputs.
+  --full  also measure the host cost of enqueueing a step on an idle GPU
+         (``host_idle_ms_per_step``) and, with N > 1, check after the timed
+         steps that every rank holds rank 0's parameters (``replicas_identical``).
   N > 1 either under torch.distributed.run (one rank per GPU; WORLD_SIZE must
   equal N) or stand-alone, in which case this script launches the N ranks
   itself (a child ``torch.distributed.run``) before touching any GPU and
@@ -65,6 +73,27 @@ def _self_launch(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(outputs: dict, out_dir: str) -> list:
+    """Write every array as ``out_dir/<name>.npy`` (float32); returns the names.
+
+    Arrays that together would pass DUMP_LIMIT_BYTES are each cut down to an
+    equal share: a fixed, seeded sample of their elements, in index order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(outputs)) // 4  # elements per array
+    over = sum(a.size for a in outputs.values()) * 4 > DUMP_LIMIT_BYTES
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if over and a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name.replace("/", "_") + ".npy"), a)
+    return sorted(outputs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -80,8 +109,14 @@ def main():
     ap.add_argument("--no-teacher-stream", action="store_true")
     ap.add_argument("--no-train-kernels", action="store_true",
                     help="student conv+BN through MIOpen instead of the native kernels (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beside the headline figure")
     ap.add_argument("opts", nargs=argparse.REMAINDER)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
@@ -109,7 +144,8 @@ def main():
     mda_nn.set_train_kernels(not args.no_train_kernels)
     r = benchmark.run(args.cfg, per_gpu, args.steps, args.warmup, opts=args.opts,
                       use_graph=not args.no_graph, backend=args.backend, dtype=args.dtype,
-                      teacher_stream=not args.no_teacher_stream, check_replicas=True)
+                      teacher_stream=not args.no_teacher_stream, check_replicas=args.full,
+                      host_idle=args.full, keep_outputs=args.dump_outputs is not None)
     if r["rank"] == 0:
         n = r["n_gpus"]
         if n != args.gpus:
@@ -148,8 +184,11 @@ def main():
             "replicas_identical": r.get("replicas_identical"),
             "final_loss": round(r["final_loss"], 4),
             "host_ms_per_step": round(r["host_ms_per_step"], 4),
-            "host_idle_ms_per_step": round(r["host_idle_ms_per_step"], 4),
+            "host_idle_ms_per_step": (round(r["host_idle_ms_per_step"], 4)
+                                      if r["host_idle_ms_per_step"] is not None else None),
         }
+        if args.dump_outputs is not None:
+            out["outputs"] = _dump_outputs(r["outputs"], args.dump_outputs)
         print(json.dumps(out), flush=True)
     D.destroy()
 

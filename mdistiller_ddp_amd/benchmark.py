@@ -58,7 +58,11 @@ def _calibrate_random_teacher(distiller, ds, dev) -> None:
 
 def run(cfg_file: str, per_gpu_batch: int, steps: int, warmup: int, opts=(), use_graph=True,
         backend="auto", dtype="bf16", teacher_stream=True, dataset=None, crd_k=None,
-        check_replicas=False):
+        check_replicas=False, host_idle=True, keep_outputs=False):
+    """``host_idle``: also measure the host cost of enqueueing one step on an
+    idle GPU (10 more steps after the timed ones).  ``keep_outputs``: return, as
+    ``"outputs"``, what the last timed ``TrainStep.step`` call handed back
+    (``preds`` and every loss) as float32 numpy arrays."""
     from .ops.backend import set_backend
     from .parallel import dist as D
     from .config import get_cfg
@@ -118,9 +122,11 @@ def run(cfg_file: str, per_gpu_batch: int, steps: int, warmup: int, opts=(), use
     # beside this step's student work (TrainStep teacher look-ahead)
     cur = next(it)
 
+    last = [None]  # what the latest step returned: device (preds, losses)
+
     def advance(b):
         nb = next(it)
-        step.step(b, next_batch=nb)
+        last[0] = step.step(b, next_batch=nb)
         return nb
 
     # the set-up objects (models, graphs, earlier configs in this process) move to
@@ -155,10 +161,18 @@ def run(cfg_file: str, per_gpu_batch: int, steps: int, warmup: int, opts=(), use
     if D.is_dist():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     el = float(t.item())
+    outputs = None
+    if keep_outputs and last[0] is not None:
+        # copied out before any further step: a replayed graph hands back the
+        # same static buffers every step
+        preds, losses = last[0]
+        outputs = {"preds": preds.detach().float().cpu().numpy()}
+        for name, v in losses.items():
+            outputs[name] = v.detach().float().cpu().numpy()
     # host cost of enqueueing one step with an idle GPU (no queue back-pressure):
     # the launch-bound floor of the step
     hs = []
-    for _ in range(10):
+    for _ in range(10 if host_idle else 0):
         sync()
         h0 = time.perf_counter()
         cur = advance(cur)
@@ -181,7 +195,8 @@ def run(cfg_file: str, per_gpu_batch: int, steps: int, warmup: int, opts=(), use
         "seconds": el,
         "ms_per_step": 1000.0 * el / steps,
         "host_ms_per_step": 1000.0 * host / steps,
-        "host_idle_ms_per_step": 1000.0 * sorted(hs)[len(hs) // 2],
+        "host_idle_ms_per_step": 1000.0 * sorted(hs)[len(hs) // 2] if hs else None,
+        "outputs": outputs,
         "images_per_s": n * per_gpu_batch * steps / el,
         "n_gpus": n,
         "global_batch": n * per_gpu_batch,

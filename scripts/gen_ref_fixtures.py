@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Generate the reference-parity fixtures once (``tests/fixtures/``).
+"""Generate the reference-parity fixtures once (``tests/fixtures/``, and
+``tests/golden/`` for the sets stored in parts).
 
 Runs the reference's own loss functions, DOT optimizer and ShuffleNetV1
 (read-only sources under ``$MDA_REFERENCE``, default /root/reference) on
@@ -21,6 +22,7 @@ from safetensors.torch import save_file
 
 REF = os.environ.get("MDA_REFERENCE", "/root/reference")
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "fixtures")
+GOLDEN = os.path.join(os.path.dirname(OUT), "golden")
 
 
 def _pkg(name, path):
@@ -264,14 +266,51 @@ def shufflenet_full_shapes():
     return {k: list(v.shape) for k, v in net.state_dict().items()}
 
 
+def det_reviewkd():
+    """The detection tree's ReviewKD chain (``detection/model/reviewkd.py``) on
+    five FPN-shaped levels and its HCL loss: (parameters + features, outputs +
+    HCL targets + loss), two files to keep each under 1 MiB."""
+    mod = _exec("_r_det_reviewkd", os.path.join(REF, "detection", "model", "reviewkd.py"))
+    torch.manual_seed(0)
+    net = mod.ReviewKD([32] * 5, [32] * 5, 32).train()
+    a = {f"sd/{k}": v.clone().contiguous() for k, v in net.state_dict().items()}
+    feats = [torch.randn(2, 32, s, s) for s in (32, 16, 8, 4, 2)]
+    with torch.no_grad():
+        out = net([f.clone() for f in feats])
+    tgt = [torch.randn_like(x) for x in out]
+    b = {"hcl": mod.hcl(out, tgt).detach().reshape(())}
+    for i, (f, o, t) in enumerate(zip(feats, out, tgt)):
+        a[f"feat{i}"], b[f"out{i}"], b[f"target{i}"] = f, o.contiguous(), t
+    return a, b
+
+
+SHUV1_PARTS = {"sd": ("sd/", "x"), "t0": ("t0/",), "t1": ("t1/",), "grad": ("grad/",)}
+
+
+def save_parts(d, name, parts=SHUV1_PARTS):
+    """Store ``d`` under tests/golden/ as ``<name>.<part>.safetensors``, split by
+    key prefix so that every file stays under 1 MiB (tests/_fixtures.py::load
+    puts them together again)."""
+    left = dict(d)
+    for part, prefixes in parts.items():
+        sub = {k: left.pop(k) for k in list(left) if k.startswith(prefixes)}
+        path = os.path.join(GOLDEN, f"{name}.{part}.safetensors")
+        save_file(sub, path)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) < 1 << 20, path
+    assert not left, sorted(left)
+
+
 if __name__ == "__main__":
     import json
     os.makedirs(OUT, exist_ok=True)
+    os.makedirs(GOLDEN, exist_ok=True)
+    a, b = det_reviewkd()
+    save_file(a, os.path.join(GOLDEN, "ref_det_reviewkd_inputs.safetensors"))
+    save_file(b, os.path.join(GOLDEN, "ref_det_reviewkd_outputs.safetensors"))
     with open(os.path.join(OUT, "ref_shufflev1_shapes.json"), "w") as f:
         json.dump(shufflenet_full_shapes(), f, indent=0, sort_keys=True)
     a = losses()
     save_file(a, os.path.join(OUT, "ref_losses.safetensors"))
-    b = shufflenet()
-    save_file(b, os.path.join(OUT, "ref_shufflenetv1.safetensors"))
-    for f in ("ref_losses.safetensors", "ref_shufflenetv1.safetensors"):
-        print(f, os.path.getsize(os.path.join(OUT, f)))
+    print("ref_losses.safetensors", os.path.getsize(os.path.join(OUT, "ref_losses.safetensors")))
+    save_parts(shufflenet(), "ref_shufflenetv1")

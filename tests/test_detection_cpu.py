@@ -1,7 +1,7 @@
 """Detection side tree on the CPU: RCNNKD (DKD / ReviewKD / ReviewDKD, with and
 without masks) forward + backward on tiny synthetic batches, ROI sampling
 invariants, ReviewKD chain + HCL parity with the reference module
-(`detection/model/reviewkd.py`, loaded read-only), the COCO evaluator, and
+(`detection/model/reviewkd.py`, its stored outputs), the COCO evaluator, and
 the train_net CLI with checkpoint/resume."""
 import importlib.util
 import json
@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 import torch
+from safetensors.torch import load_file
 
 from mdistiller_ddp_amd.detection.config import get_det_cfg, merge_det_file
 from mdistiller_ddp_amd.detection.data import build_detection_data
@@ -19,7 +20,7 @@ from mdistiller_ddp_amd.detection.rcnn import build_kd_trans, build_model, hcl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFGS = os.path.join(ROOT, "detection", "configs")
-REF_REVIEWKD = "/root/reference/detection/model/reviewkd.py"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def tiny_cfg(path, mask=None):
@@ -95,26 +96,25 @@ def test_roi_sampling_invariants():
         assert ((s.gt_classes == K) | fg).all()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_REVIEWKD), reason="reference tree not mounted")
 def test_reviewkd_chain_and_hcl_match_reference():
-    spec = importlib.util.spec_from_file_location("_ref_det_reviewkd", REF_REVIEWKD)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    torch.manual_seed(0)
+    # the reference module's parameters, inputs, outputs and HCL value, stored by
+    # scripts/gen_ref_fixtures.py::det_reviewkd
+    inp = load_file(os.path.join(GOLDEN, "ref_det_reviewkd_inputs.safetensors"))
+    ref = load_file(os.path.join(GOLDEN, "ref_det_reviewkd_outputs.safetensors"))
     ours = build_kd_trans(None, channels=32, levels=5).train()
-    theirs = ref.ReviewKD([32] * 5, [32] * 5, 32).train()
     # parameter order matches: abfs reversed in both
-    sd = {k: v for k, v in ours.state_dict().items()}
-    theirs_sd = theirs.state_dict()
-    assert set(sd) == set(theirs_sd)
-    theirs.load_state_dict(sd)
-    feats = [torch.randn(2, 32, s, s) for s in (32, 16, 8, 4, 2)]
+    theirs_sd = {k[3:]: v for k, v in inp.items() if k.startswith("sd/")}
+    assert set(ours.state_dict()) == set(theirs_sd)
+    ours.load_state_dict(theirs_sd)
+    feats = [inp[f"feat{i}"] for i in range(5)]
+    assert [f.shape[-1] for f in feats] == [32, 16, 8, 4, 2]
     a = ours([f.clone() for f in feats])
-    b = theirs([f.clone() for f in feats])
+    b = [ref[f"out{i}"] for i in range(5)]
+    assert len(a) == len(b)
     for x, y in zip(a, b):
         torch.testing.assert_close(x, y, atol=1e-4, rtol=1e-4)
-    t = [torch.randn_like(x) for x in a]
-    torch.testing.assert_close(hcl(a, t), ref.hcl(b, t), atol=1e-5, rtol=1e-5)
+    t = [ref[f"target{i}"] for i in range(5)]
+    torch.testing.assert_close(hcl(a, t), ref["hcl"], atol=1e-5, rtol=1e-5)
 
 
 def test_coco_evaluator_perfect_and_empty():

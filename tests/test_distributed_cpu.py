@@ -171,7 +171,8 @@ def test_global_rank_is_rank_not_local_rank():
 
 
 def test_bench_self_launch_two_ranks_cpu():
-    """``python bench.py --gpus 2`` launches 2 ranks itself and reports n_gpus 2."""
+    """``python bench.py --gpus 2`` launches 2 ranks itself and reports n_gpus 2
+    (``--full``: the replica check is not part of a plain run)."""
     import json
     import subprocess
     import sys
@@ -181,7 +182,7 @@ def test_bench_self_launch_two_ranks_cpu():
     for scaling, want_global in (("weak", 8), ("strong", 4)):
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                               "--steps", "1", "--warmup", "1", "--batch", "4", "--global-batch", "4",
-                              "--scaling", scaling, "DISTILLER.STUDENT", "resnet8",
+                              "--scaling", scaling, "--full", "DISTILLER.STUDENT", "resnet8",
                               "DISTILLER.TEACHER", "resnet20"],
                              capture_output=True, text=True, timeout=600, env=env, cwd=root)
         assert out.returncode == 0, out.stderr[-3000:]
