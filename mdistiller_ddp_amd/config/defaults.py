@@ -32,7 +32,10 @@ CFG.DATASET.TEST = CN()
 CFG.DATASET.TEST.BATCH_SIZE = 64
 CFG.DATASET.SYNTHETIC = False        # ext: device-resident synthetic data of the dataset's shape
 CFG.DATASET.SYNTHETIC_SIZE = 0       # ext: #train samples for synthetic data (0 = real dataset size)
-CFG.DATASET.GPU_AUG = True           # ext: crop/flip/normalise on device (HIP kernel)
+# ext: Tiny-ImageNet device-resident with rotate/flip/normalise on device (HIP kernel); False =
+# PIL workers over the folder tree.  CIFAR-100 is always on device and ImageNet always on the
+# folder path: both ignore the key
+CFG.DATASET.GPU_AUG = True
 CFG.DATASET.ROOT = ""                # ext: data root ('' = <repo>/data)
 
 # Distiller ----------------------------------------------------------------

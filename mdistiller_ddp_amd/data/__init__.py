@@ -6,7 +6,10 @@ Tiny-ImageNet, CRD-sample variants when the distiller is CRD).  Here:
 * ``DATASET.SYNTHETIC`` -- random uint8 images of the dataset's shape through
   the device-resident pipeline (no files needed; used by tests/benches).
 * cifar100 -- device-resident set + HIP crop/flip/normalise kernel.
-* imagenet / tiny_imagenet -- folder datasets decoded by CPU workers.
+* tiny_imagenet -- with ``DATASET.GPU_AUG`` (the default) a device-resident
+  set packed once from the folder tree + HIP rotate/flip/normalise kernel;
+  without it the folder path below.
+* imagenet -- folder dataset decoded by CPU workers (it does not fit in HBM).
 
 ``cfg.SOLVER.BATCH_SIZE`` / ``cfg.DATASET.TEST.BATCH_SIZE`` are per-rank
 batch sizes here (``tools/train.py`` divides the global ones by world size).
@@ -38,6 +41,9 @@ def get_dataset(cfg, device="cpu"):
     elif typ == "cifar100":
         from .cifar100 import get_cifar100_loaders
         train, val, n = get_cifar100_loaders(cfg, device, crd)
+    elif typ == "tiny_imagenet" and cfg.DATASET.GPU_AUG:
+        from .tiny_imagenet import get_tiny_device_loaders
+        train, val, n = get_tiny_device_loaders(cfg, device, crd)
     else:
         from .imagefolder import get_folder_dataloaders
         train, val, n = get_folder_dataloaders(cfg, typ, crd)

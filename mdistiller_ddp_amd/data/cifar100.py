@@ -100,12 +100,66 @@ def augment_ref(x: torch.Tensor, idx: torch.Tensor, offs: torch.Tensor, flip: to
     return (img - m) / s
 
 
+def rotate_coef(deg: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """int32 [B, 6]: the output->source affine map of a rotation by ``deg``
+    degrees (counter-clockwise, about the image centre, like PIL's
+    ``Image.rotate``) in 16.16 fixed point.
+
+    ``sx = a0 (x+1/2) + a1 (y+1/2) + a2``, ``sy = a3 (x+1/2) + a4 (y+1/2) + a5``;
+    built in fp32 on ``deg``'s device, each stored as ``floor(v * 65536 + 0.5)``.
+    """
+    th = deg.float() * (-math.pi / 180.0)
+    a0, a1 = torch.cos(th), torch.sin(th)
+    a3, a4 = -a1, a0
+    a2 = -a0 * w / 2 - a1 * h / 2 + w / 2
+    a5 = -a3 * w / 2 - a4 * h / 2 + h / 2
+    a = torch.stack([a0, a1, a2, a3, a4, a5], dim=1)
+    return torch.floor(a * 65536.0 + 0.5).to(torch.int32)
+
+
+def rotate_flip_u8_ref(x: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor,
+                       flip: torch.Tensor) -> torch.Tensor:
+    """PyTorch reference of the rotate kernel's pixel selection: uint8 [B, H, W, C].
+
+    Nearest-neighbour rotation by the fixed-point map ``coef``
+    (:func:`rotate_coef`) with fill 0, then the horizontal flip of the rotated
+    image: output ``(x, y)`` reads source ``(sx, sy)`` of ``xs = W-1-x`` (flipped)
+    or ``x``, all in int64 -- ``sx = (a0 (2 xs + 1) + a1 (2 y + 1) + 2 a2) >> 17``.
+    """
+    g = x[idx.long()]
+    b, h, w, c = g.shape
+    dev = g.device
+    a = coef.long().view(b, 6, 1, 1)
+    xs = torch.arange(w, device=dev).view(1, w).expand(b, w)
+    xs = torch.where(flip.bool().view(b, 1), w - 1 - xs, xs)
+    u = (2 * xs + 1).view(b, 1, w)
+    v = (2 * torch.arange(h, device=dev) + 1).view(1, h, 1)
+    sx = torch.div(a[:, 0] * u + a[:, 1] * v + 2 * a[:, 2], 1 << 17, rounding_mode="floor")
+    sy = torch.div(a[:, 3] * u + a[:, 4] * v + 2 * a[:, 5], 1 << 17, rounding_mode="floor")
+    ok = (sx >= 0) & (sx < w) & (sy >= 0) & (sy < h)
+    lin = (sy.clamp(0, h - 1) * w + sx.clamp(0, w - 1)).view(b, h * w, 1).expand(b, h * w, c)
+    out = g.reshape(b, h * w, c).gather(1, lin).view(b, h, w, c)
+    return torch.where(ok.view(b, h, w, 1), out, torch.zeros_like(out))
+
+
+def rotate_flip_ref(x: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor, flip: torch.Tensor,
+                    mean=CIFAR100_MEAN, std=CIFAR100_STD) -> torch.Tensor:
+    """:func:`rotate_flip_u8_ref` followed by ToTensor + Normalize: float32 NCHW."""
+    img = rotate_flip_u8_ref(x, idx, coef, flip).permute(0, 3, 1, 2).float() / 255.0
+    c = img.shape[1]
+    m = torch.tensor(mean[:c], device=img.device).view(1, c, 1, 1)
+    s = torch.tensor(std[:c], device=img.device).view(1, c, 1, 1)
+    return (img - m) / s
+
+
 class DeviceImageLoader:
     """Device-resident image set with on-device augmentation.
 
     ``x`` uint8 [N, H, W, C] (numpy or tensor), ``y`` int labels.  ``train``
-    enables the random crop (zero padding ``pad``) and horizontal flip; the
-    eval path is a plain normalise.  Shards by rank with an epoch-seeded
+    enables the random crop (zero padding ``pad``) and horizontal flip, or,
+    with ``rotate > 0``, a random rotation by up to ``rotate`` degrees either
+    way (nearest neighbour, fill 0) followed by the flip; ``pad`` and
+    ``rotate`` exclude each other.  The eval path is a plain normalise.  Shards by rank with an epoch-seeded
     shuffle (:class:`ShardSampler`); ``index_map`` maps dataset indices to
     stored rows (synthetic sets store fewer rows than they index).
     """
@@ -113,7 +167,9 @@ class DeviceImageLoader:
     def __init__(self, x, y, batch_size: int, device, train: bool = True, out_dtype=torch.float32,
                  mean=CIFAR100_MEAN, std=CIFAR100_STD, pad: int = 4, shuffle=None,
                  drop_last: bool = False, crd: CRDSampler | None = None, seed: int = 0,
-                 num_data: int | None = None, channels_last: bool = True):
+                 num_data: int | None = None, channels_last: bool = True, rotate: float = 0.0):
+        if rotate < 0 or (pad and rotate > 0):
+            raise ValueError(f"pad={pad} with rotate={rotate}: use a zero pad with a rotation >= 0")
         self.device = torch.device(device)
         self.x = torch.as_tensor(x).to(self.device)
         assert self.x.dtype == torch.uint8 and self.x.dim() == 4, "x must be uint8 [N, H, W, C]"
@@ -125,6 +181,7 @@ class DeviceImageLoader:
         self.train = train
         self.out_dtype = out_dtype
         self.pad = pad if train else 0
+        self.rotate = float(rotate) if train else 0.0
         self.drop_last = drop_last
         self.crd = crd
         self.channels_last = channels_last
@@ -160,6 +217,8 @@ class DeviceImageLoader:
         """Augmented, normalised images for dataset rows ``idx`` (device int64)."""
         b = idx.shape[0]
         _, h, w, c = self.x.shape
+        if self.rotate > 0:
+            return self._make_rotated(idx)
         if self.pad:
             offs = torch.randint(0, 2 * self.pad + 1, (b, 2), generator=self.gen, device=self.device,
                                  dtype=torch.int32)
@@ -180,6 +239,23 @@ class DeviceImageLoader:
             img = out.permute(0, 3, 1, 2)  # NCHW view of NHWC memory = channels_last
             return img if self.channels_last else img.contiguous()
         img = augment_ref(self.x, idx, offs, flip, self._mean, self._std, self.pad).to(self.out_dtype)
+        return img.contiguous(memory_format=torch.channels_last) if self.channels_last else img
+
+    def _make_rotated(self, idx: torch.Tensor) -> torch.Tensor:
+        b = idx.shape[0]
+        _, h, w, c = self.x.shape
+        deg = (torch.rand(b, generator=self.gen, device=self.device) * 2 - 1) * self.rotate
+        flip = torch.randint(0, 2, (b,), generator=self.gen, device=self.device, dtype=torch.uint8)
+        coef = rotate_coef(deg, h, w)
+        from ..ops.backend import hip_enabled_for
+        if hip_enabled_for(self.x) and self.out_dtype in (torch.float32, torch.bfloat16):
+            from ..ops import _ext
+            out = torch.empty(b, h, w, c, dtype=self.out_dtype, device=self.device)
+            _ext.call("mda_rotate_flip_norm", self.x, idx.contiguous(), coef, flip, self.mean,
+                      self.inv_std, out, 0 if self.out_dtype == torch.float32 else 1, b, h, w, c)
+            img = out.permute(0, 3, 1, 2)
+            return img if self.channels_last else img.contiguous()
+        img = rotate_flip_ref(self.x, idx, coef, flip, self._mean, self._std).to(self.out_dtype)
         return img.contiguous(memory_format=torch.channels_last) if self.channels_last else img
 
     def __iter__(self):

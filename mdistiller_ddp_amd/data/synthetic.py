@@ -7,7 +7,8 @@ Two flavours:
   like the reference's "training time" inset).
 * :func:`synthetic_loaders` -- random uint8 images of the dataset's shape fed
   through the real device-resident pipeline (:class:`DeviceImageLoader`:
-  shard sampler, on-device crop/flip/normalise kernel, CRD sampler), used by
+  shard sampler, on-device crop/flip/normalise kernel -- rotate/flip/normalise
+  for Tiny-ImageNet --, CRD sampler), used by
   ``DATASET.SYNTHETIC`` so the trainer/CLI exercise every data-path piece.
 """
 from __future__ import annotations
@@ -105,8 +106,9 @@ def synthetic_loaders(cfg, device, crd: bool):
     xtr = rng.integers(0, 256, (rows, h, w, c), dtype=np.uint8)
     xva = rng.integers(0, 256, (rows_v, h, w, c), dtype=np.uint8)
     pad = 4 if name == "cifar100" else 0
+    rotate = 20.0 if name == "tiny_imagenet" else 0.0
     train = DeviceImageLoader(xtr, y_rows, cfg.SOLVER.BATCH_SIZE, device, train=True, mean=mean,
-                              std=std, pad=pad, crd=sampler, seed=seed, num_data=n)
+                              std=std, pad=pad, rotate=rotate, crd=sampler, seed=seed, num_data=n)
     val = DeviceImageLoader(xva, yva, cfg.DATASET.TEST.BATCH_SIZE, device, train=False,
                             mean=mean, std=std, num_data=nv)
     return train, val, n

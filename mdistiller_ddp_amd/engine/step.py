@@ -208,9 +208,7 @@ class TrainStep:
         self.deterministic = bool(cfg.EXPERIMENT.get("DETERMINISTIC", False))
         if self.device.type == "cuda":
             from ..ops import hip_train as _ht
-            _ht.set_deterministic(self.deterministic)
-            if self.deterministic:
-                torch.backends.cudnn.deterministic = True
+            _ht.set_deterministic(self.deterministic)  # torch.backends.cudnn.deterministic too
         self.flat = FlatParams(distiller.get_learnable_parameters(), 2 if self.is_dot else 1)
         self.opt = build_optimizer(cfg, self.flat, grad_scale=1.0 / self.world, trainer=trainer)
         self.use_graph = (bool(use_graph) and self.device.type == "cuda"

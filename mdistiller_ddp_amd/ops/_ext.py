@@ -140,6 +140,7 @@ SIGNATURES = {
     "mda_deform_col2im": "i" + "pppp" + "ppp" + "p" + "s",
     # data augmentation (csrc/aug.hip)
     "mda_crop_flip_norm": "ppppppp" + "iiiiii" + "s",
+    "mda_rotate_flip_norm": "ppppppp" + "iiiii" + "s",
     # optimizers (csrc/optim.hip)
     "mda_sgd_step": "ppppfffpfis",
     "mda_dot_step": "pppppppffffiis",

@@ -716,15 +716,19 @@ def set_deterministic(on: bool) -> None:
     ``MDA_BN_FUSED=0`` kernels), and the fusions that exist only on the
     regions (VirtualBN, BnLink sums) are off.  Everything else is fixed-order in both modes (split-K
     combines, weight-gradient partial reduces, losses, optimizer, VID).
-    Turning it off restores the switches as they were."""
+    PyTorch's layers follow (``torch.backends.cudnn.deterministic``).
+    Turning it off restores the switches, that flag included, as they were:
+    the flag is process-global, and left on it changes the MIOpen algorithms
+    of every later, non-deterministic step in the process."""
     on = bool(on)
     if on == _DET["on"]:
         return
     if on:
-        _DET["saved"] = (_BN_FUSED[0], _BNB_ON[0], _VRES_ON[0])
+        _DET["saved"] = (_BN_FUSED[0], _BNB_ON[0], _VRES_ON[0], torch.backends.cudnn.deterministic)
         _BN_FUSED[0] = _BNB_ON[0] = _VRES_ON[0] = False
+        torch.backends.cudnn.deterministic = True
     else:
-        (_BN_FUSED[0], _BNB_ON[0], _VRES_ON[0]) = _DET["saved"]
+        (_BN_FUSED[0], _BNB_ON[0], _VRES_ON[0], torch.backends.cudnn.deterministic) = _DET["saved"]
     _DET["on"] = on
 
 
