@@ -102,7 +102,8 @@ class DeviceMeters:
             v = losses[k].detach().double().reshape(())
             b[1 + i] += v
             total = v if total is None else total + v
-        b[0] += total
+        if total is not None:  # no loss keys: only the hit counts
+            b[0] += total
         n = len(self.loss_keys)
         rank = topk_rank(preds.detach(), target)
         b[n + 1] += (rank < 1).sum().double()
