@@ -121,6 +121,7 @@ CFG.KD.TEMPERATURE = 4
 CFG.KD.LOSS = CN()
 CFG.KD.LOSS.CE_WEIGHT = 0.1
 CFG.KD.LOSS.KD_WEIGHT = 0.9
+CFG.KD.LOGIT_STAND = False           # ext: z-score student / teacher logits before the KD softmax
 
 CFG.AT = CN()
 CFG.AT.P = 2
@@ -213,6 +214,7 @@ CFG.DKD.ALPHA = 1.0
 CFG.DKD.BETA = 8.0
 CFG.DKD.T = 4.0
 CFG.DKD.WARMUP = 20
+CFG.DKD.LOGIT_STAND = False          # ext: z-score student / teacher logits before TCKD / NCKD
 
 METHOD_NODES = ("KD", "AT", "RKD", "FITNET", "KDSVD", "OFD", "NST", "PKT", "SP",
                 "VID", "CRD", "REVIEWKD", "DKD")

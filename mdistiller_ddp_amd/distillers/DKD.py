@@ -5,7 +5,8 @@ TCKD is the KL between the binary (target, non-target) distributions and
 NCKD the KL between the softmaxes over the non-target classes.  The fused HIP
 kernel excludes the target column explicitly (the reference subtracts
 ``1000 * gt_mask`` from the tempered logits, which is the same in fp32 and
-fragile in bf16), computing everything in fp32.
+fragile in bf16), computing everything in fp32.  ``DKD.LOGIT_STAND`` z-scores the
+student and teacher logits before TCKD / NCKD (Sun et al., CVPR 2024).
 """
 from __future__ import annotations
 
@@ -22,6 +23,7 @@ class DKD(Distiller):
         self.beta = cfg.DKD.BETA
         self.temperature = cfg.DKD.T
         self.warmup = cfg.DKD.WARMUP
+        self.logit_stand = cfg.DKD.LOGIT_STAND
 
     def forward_train(self, image, target, **kwargs):
         t_out = self.teacher_forward(image)
@@ -29,5 +31,6 @@ class DKD(Distiller):
         logits_teacher, _ = t_out.get()
         loss_ce, loss_dkd = L.ce_dkd(logits_student, logits_teacher, target, self.ce_loss_weight,
                                      self.alpha, self.beta, self.temperature,
-                                     epoch=kwargs.get("epoch"), warmup=self.warmup)
+                                     epoch=kwargs.get("epoch"), warmup=self.warmup,
+                                     logit_stand=self.logit_stand)
         return logits_student, {"loss_ce": loss_ce, "loss_kd": loss_dkd}

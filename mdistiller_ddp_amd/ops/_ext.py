@@ -30,6 +30,7 @@ _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int64, "f": ctypes.c_float, "s": ctyp
 SIGNATURES = {
     # losses (csrc/losses.hip)
     "mda_logit_loss": "iiippppppppiifffffpfps",
+    "mda_logit_loss_std": "iiippppppppiifffffpfps",
     "mda_axpby": "ipppppis",
     # feature losses (csrc/feat.hip)
     "mda_at_loss": "iipppppp" + "iiii" + "fs",

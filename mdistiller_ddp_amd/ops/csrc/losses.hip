@@ -19,6 +19,18 @@
 // (mda_axpby) so the two-backward DOT trainer works unchanged; with the
 // training step's constant unit seeds it returns g_sum (or g_ce) and
 // launches nothing (ops/losses.py register_unit_seed).
+//
+// STAND variant (mda_logit_loss_std): logit standardisation (Sun et al., CVPR
+// 2024).  The KD / DKD term is evaluated on z_s / T and z_t / T, each row
+// z-scored with its own statistics,
+//   mu = mean(x), sigma = sqrt(sum (x - mu)^2 / (C - 1)), z = (x - mu) / (sigma + 1e-7)
+// while CE stays on the raw student logits.  The row statistics are two-pass
+// over the registers; the standardised values then replace the raw ones in the
+// same registers.  With g = d loss_kd / d z kept in registers, the gradient
+// w.r.t. the raw logits is
+//   (g_j - mean(g) - z_j * (sum_i g_i z_i) * k) / (sigma + 1e-7)
+//   k = (sigma + 1e-7) / ((C - 1) sigma), and k = 0 for a constant row (sigma == 0),
+// so g_kd / g_sum are stored once, after two more wave reductions.
 #include "common.h"
 
 namespace {
@@ -28,7 +40,34 @@ constexpr int MAXNPL = 32;          // C <= 2048
 
 enum { MODE_CE = 0, MODE_KD = 1, MODE_DKD = 2 };
 
-template <typename TS, typename TT, typename TG, int NPL, int MODE>
+constexpr float STAND_EPS = 1e-7f;
+
+// z-score one row held in registers, in place.  Lanes past C hold -INFINITY,
+// add nothing to either sum and stay -INFINITY.  rinv = 1 / (sigma + eps),
+// k as in the header comment.
+template <int NPL>
+__device__ __forceinline__ void standardize_row(float (&v)[NPL], int lane, int C, float& rinv,
+                                                float& k) {
+  float a = 0.f;
+#pragma unroll
+  for (int i = 0; i < NPL; ++i)
+    if (lane + 64 * i < C) a += v[i];
+  const float mu = wave_sum(a) / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NPL; ++i)
+    if (lane + 64 * i < C) {
+      const float d = v[i] - mu;
+      q += d * d;
+    }
+  const float sigma = sqrtf(wave_sum(q) / (float)(C - 1));
+  rinv = 1.f / (sigma + STAND_EPS);
+  k = sigma > 0.f ? (sigma + STAND_EPS) / ((float)(C - 1) * sigma) : 0.f;
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) v[i] = (v[i] - mu) * rinv;
+}
+
+template <typename TS, typename TT, typename TG, int NPL, int MODE, bool STAND = false>
 __global__ void __launch_bounds__(256)
 logit_loss_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
                   const int64_t* __restrict__ target, TG* __restrict__ g_ce,
@@ -87,6 +126,17 @@ logit_loss_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
       }
     }
     if (MODE == MODE_KD || MODE == MODE_DKD) {
+      // STAND: sv / tv hold the standardised rows from here on; gzv keeps
+      // d loss_kd / d z until the chain rule below
+      float gzv[STAND ? NPL : 1];
+      float rinv_s = 0.f, k_s = 0.f;
+      if (STAND) {
+        float rinv_t, k_t;
+        standardize_row<NPL>(sv, lane, C, rinv_s, k_s);
+        standardize_row<NPL>(tv, lane, C, rinv_t, k_t);
+#pragma unroll
+        for (int i = 0; i < (STAND ? NPL : 1); ++i) gzv[i] = 0.f;
+      }
       // ---- tempered softmaxes ------------------------------------------
       float ms = -INFINITY, mt = -INFINITY;
 #pragma unroll
@@ -117,8 +167,12 @@ logit_loss_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
             float p = __expf(lp);
             kl += p * (lp - lq);
             const float gk = gscale * (__expf(lq) - p);
-            io<TG>::st(g_kd, base + c, gk);
-            if (g_sum) io<TG>::st(g_sum, base + c, gcv[i] + gk);
+            if (STAND) {
+              gzv[STAND ? i : 0] = gk;
+            } else {
+              io<TG>::st(g_kd, base + c, gk);
+              if (g_sum) io<TG>::st(g_sum, base + c, gcv[i] + gk);
+            }
           }
         }
         kd_row = wave_sum(kl) * T * T;
@@ -151,7 +205,14 @@ logit_loss_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
         const float lzs_o = __logf(zs_o), lzt_o = __logf(zt_o);
         // binary (target, other) distributions in the log domain:
         // log P(other) = log sum_{j != y} exp(z_j) = m_o + log Z_o
-        const float sy = s_y * inv_T;
+        float sy = s_y * inv_T;
+        if (STAND) {
+          float v = 0.f;
+#pragma unroll
+          for (int i = 0; i < NPL; ++i)
+            if (lane + 64 * i == y) v = sv[i];
+          sy = wave_sum(v) * inv_T;
+        }
         float ty = 0.f;
 #pragma unroll
         for (int i = 0; i < NPL; ++i)
@@ -183,12 +244,37 @@ logit_loss_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
               nckd += ph * (lp - lq);
               gz = alpha * qh * tck + beta * (qh - ph);
             }
-            io<TG>::st(g_kd, base + c, gs * gz);
-            if (g_sum) io<TG>::st(g_sum, base + c, gcv[i] + gs * gz);
+            if (STAND) {
+              gzv[STAND ? i : 0] = gs * gz;
+            } else {
+              io<TG>::st(g_kd, base + c, gs * gz);
+              if (g_sum) io<TG>::st(g_sum, base + c, gcv[i] + gs * gz);
+            }
           }
         }
         nckd = wave_sum(nckd);
         kd_row = (alpha * tckd + beta * nckd) * T * T;
+      }
+      if (STAND) {
+        // ---- d/dz -> d/d(raw logits) --------------------------------------
+        float ga = 0.f, gb = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i)
+          if (lane + 64 * i < C) {
+            ga += gzv[STAND ? i : 0];
+            gb += gzv[STAND ? i : 0] * sv[i];
+          }
+        ga = wave_sum(ga) / (float)C;
+        gb = wave_sum(gb) * k_s;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+          int c = lane + 64 * i;
+          if (c < C) {
+            const float gk = rinv_s * (gzv[STAND ? i : 0] - ga - sv[i] * gb);
+            io<TG>::st(g_kd, base + c, gk);
+            if (g_sum) io<TG>::st(g_sum, base + c, gcv[i] + gk);
+          }
+        }
       }
     }
   }
@@ -223,43 +309,43 @@ logit_loss_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
   }
 }
 
-template <typename TS, typename TT, int MODE, int NPL>
+template <typename TS, typename TT, int MODE, int NPL, bool STAND = false>
 int launch_t(const void* s, const void* t, const int64_t* y, void* gce, void* gkd, float* part,
              unsigned* cnt, float* losses, int B, int C, float invT, float cew, float kdw, float a,
              float b, const float* ep, float wu, void* gsum, hipStream_t st) {
   dim3 grid((B + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-  hipLaunchKernelGGL((logit_loss_kernel<TS, TT, TS, NPL, MODE>), grid, dim3(256), 0, st,
+  hipLaunchKernelGGL((logit_loss_kernel<TS, TT, TS, NPL, MODE, STAND>), grid, dim3(256), 0, st,
                      (const TS*)s, (const TT*)t, y, (TS*)gce, (TS*)gkd, part, cnt, losses, B, C,
                      invT, cew, kdw, a, b, ep, wu, (TS*)gsum);
   MDA_CHECK_LAUNCH();
 }
 
-template <typename TS, typename TT, int MODE>
+template <typename TS, typename TT, int MODE, bool STAND = false>
 int launch_npl(const void* s, const void* t, const int64_t* y, void* gce, void* gkd, float* part,
                unsigned* cnt, float* losses, int B, int C, float invT, float cew, float kdw,
                float a, float b, const float* ep, float wu, void* gsum, hipStream_t st) {
   int npl = (C + 63) / 64;
 #define NPL_CASE(N)                                                                          \
   if (npl <= N)                                                                              \
-    return launch_t<TS, TT, MODE, N>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, \
-                                     kdw, a, b, ep, wu, gsum, st);
+    return launch_t<TS, TT, MODE, N, STAND>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, \
+                                            cew, kdw, a, b, ep, wu, gsum, st);
   NPL_CASE(2) NPL_CASE(4) NPL_CASE(8) NPL_CASE(16) NPL_CASE(32)
 #undef NPL_CASE
   return (int)hipErrorInvalidValue;
 }
 
-template <int MODE>
+template <int MODE, bool STAND = false>
 int launch_mode(int dts, int dtt, const void* s, const void* t, const int64_t* y, void* gce,
                 void* gkd, float* part, unsigned* cnt, float* losses, int B, int C, float invT,
                 float cew, float kdw, float a, float b, const float* ep, float wu, void* gs,
                 hipStream_t st) {
   if (dts == DT_F32 && dtt == DT_F32)
-    return launch_npl<float, float, MODE>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
+    return launch_npl<float, float, MODE, STAND>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
   if (dts == DT_BF16 && dtt == DT_BF16)
-    return launch_npl<bf16_t, bf16_t, MODE>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
+    return launch_npl<bf16_t, bf16_t, MODE, STAND>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
   if (dts == DT_BF16 && dtt == DT_F32)
-    return launch_npl<bf16_t, float, MODE>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
-  return launch_npl<float, bf16_t, MODE>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
+    return launch_npl<bf16_t, float, MODE, STAND>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
+  return launch_npl<float, bf16_t, MODE, STAND>(s, t, y, gce, gkd, part, cnt, losses, B, C, invT, cew, kdw, a, b, ep, wu, gs, st);
 }
 
 // out = (*a) * x + (*b) * y ; a/b are device scalars (graph-replay safe).
@@ -292,6 +378,21 @@ MDA_API int mda_logit_loss(int64_t mode, int64_t dts, int64_t dtt, const void* s
   if (mode == MODE_KD)
     return launch_mode<MODE_KD>(dts, dtt, s, t, y, g_ce, g_kd, partial, counter, losses, B, C, inv_T, ce_w, kd_w, alpha, beta, epoch, warmup, g_sum, st);
   return launch_mode<MODE_DKD>(dts, dtt, s, t, y, g_ce, g_kd, partial, counter, losses, B, C, inv_T, ce_w, kd_w, alpha, beta, epoch, warmup, g_sum, st);
+}
+
+// mda_logit_loss with logit standardisation of the KD / DKD term (mode 1 or 2, C >= 2)
+MDA_API int mda_logit_loss_std(int64_t mode, int64_t dts, int64_t dtt, const void* s,
+                               const void* t, const int64_t* y, void* g_ce, void* g_kd,
+                               float* partial, unsigned* counter, float* losses, int64_t B,
+                               int64_t C, float inv_T, float ce_w, float kd_w, float alpha,
+                               float beta, const float* epoch, float warmup, void* g_sum,
+                               hipStream_t st) {
+  if (C > 64 * MAXNPL || C < 2 || B <= 0) return (int)hipErrorInvalidValue;
+  if (mode == MODE_KD)
+    return launch_mode<MODE_KD, true>(dts, dtt, s, t, y, g_ce, g_kd, partial, counter, losses, B, C, inv_T, ce_w, kd_w, alpha, beta, epoch, warmup, g_sum, st);
+  if (mode == MODE_DKD)
+    return launch_mode<MODE_DKD, true>(dts, dtt, s, t, y, g_ce, g_kd, partial, counter, losses, B, C, inv_T, ce_w, kd_w, alpha, beta, epoch, warmup, g_sum, st);
+  return (int)hipErrorInvalidValue;
 }
 
 MDA_API int mda_axpby(int64_t dt, const float* a, const void* x, const float* b, const void* y,

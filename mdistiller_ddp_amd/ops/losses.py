@@ -7,6 +7,12 @@ logits once and produces both scalar losses and both gradients w.r.t. the
 student logits; the autograd backward is a single ``axpby`` that scales the
 stored gradients by the incoming loss gradients (device scalars, so it is
 hipGraph-replay safe and works with the two-backward DOT trainer).
+
+``logit_stand=True`` (``KD.LOGIT_STAND`` / ``DKD.LOGIT_STAND``) evaluates the KD
+or DKD term on the z-scored student and teacher rows
+(:func:`standardize_logits`; Sun et al., CVPR 2024) through the kernel's
+``STAND`` variant, ``mda_logit_loss_std``.  CE stays on the raw logits and the
+gradients stay with respect to the raw logits, so the backward is shared.
 """
 from __future__ import annotations
 
@@ -20,7 +26,23 @@ from .backend import hip_enabled_for
 # PyTorch references
 
 
-def kd_loss_ref(logits_student, logits_teacher, temperature):
+STAND_EPS = 1e-7
+
+
+def standardize_logits(x):
+    """Row-wise z-score of the logits (Sun et al., CVPR 2024): ``(x - mean) /
+    (std + 1e-7)`` with the unbiased standard deviation.  A constant row gives
+    zeros; ``torch.std``'s backward treats it as ``sigma`` having no gradient."""
+    if x.shape[-1] < 2:
+        raise ValueError("logit standardisation needs at least 2 classes, got {}".format(x.shape[-1]))
+    x = x.float()
+    return (x - x.mean(dim=-1, keepdim=True)) / (x.std(dim=-1, keepdim=True) + STAND_EPS)
+
+
+def kd_loss_ref(logits_student, logits_teacher, temperature, logit_stand=False):
+    if logit_stand:
+        logits_student = standardize_logits(logits_student)
+        logits_teacher = standardize_logits(logits_teacher)
     log_pred_student = F.log_softmax(logits_student.float() / temperature, dim=1)
     pred_teacher = F.softmax(logits_teacher.float() / temperature, dim=1)
     loss = F.kl_div(log_pred_student, pred_teacher, reduction="none").sum(1).mean()
@@ -31,9 +53,12 @@ def _gt_mask(logits, target):
     return torch.zeros_like(logits, dtype=torch.bool).scatter_(1, target.reshape(-1, 1), True)
 
 
-def dkd_loss_ref(logits_student, logits_teacher, target, alpha, beta, temperature):
+def dkd_loss_ref(logits_student, logits_teacher, target, alpha, beta, temperature,
+                 logit_stand=False):
     s = logits_student.float()
     t = logits_teacher.float()
+    if logit_stand:
+        s, t = standardize_logits(s), standardize_logits(t)
     gt = _gt_mask(s, target)
     other = ~gt
     ps = F.softmax(s / temperature, dim=1)
@@ -103,7 +128,8 @@ def _supported(s, t, C):
 
 class _LogitLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, s, t, target, mode, inv_T, ce_w, kd_w, alpha, beta, epoch=None, warmup=0.0):
+    def forward(ctx, s, t, target, mode, inv_T, ce_w, kd_w, alpha, beta, epoch=None, warmup=0.0,
+                stand=False):
         s = s.contiguous()
         t = s if t is None else t.contiguous()
         target = target.contiguous().to(torch.int64)
@@ -115,8 +141,10 @@ class _LogitLoss(torch.autograd.Function):
         g_sum = torch.empty_like(s) if (mode != 0 and _DUAL[0] is None) else None
         losses = torch.empty(2, dtype=torch.float32, device=s.device)
         ws = workspace(s.device)
-        _ext.call("mda_logit_loss", mode, _DT[s.dtype], _DT[t.dtype], s, t, target, g_ce, g_kd,
-                  ws.partial, ws.counter, losses, B, C, inv_T, ce_w, kd_w, alpha, beta,
+        # the standardised variant also returns gradients w.r.t. the raw logits,
+        # so the backward below is the same for both
+        _ext.call("mda_logit_loss_std" if stand else "mda_logit_loss", mode, _DT[s.dtype],
+                  _DT[t.dtype], s, t, target, g_ce, g_kd, ws.partial, ws.counter, losses, B, C, inv_T, ce_w, kd_w, alpha, beta,
                   _epoch_ptr(epoch, warmup), float(warmup or 0.0), g_sum)
         ctx.save_for_backward(g_ce, g_kd, g_sum)
         ctx.mode = mode
@@ -129,18 +157,18 @@ class _LogitLoss(torch.autograd.Function):
         g_ce, g_kd, g_sum = ctx.saved_tensors
         from .hip_train import _DUAL, dual_alloc
         if go_ce is None and go_kd is None:
-            return (None,) * 11
+            return (None,) * 12
         if _DUAL[0] is None:
             # the training step's constant unit seeds: nothing to scale
             uce, ukd = _is_unit(go_ce), _is_unit(go_kd)
             if ctx.mode == 0 or go_kd is None:
                 if uce:
-                    return (g_ce,) + (None,) * 10
+                    return (g_ce,) + (None,) * 11
             elif go_ce is None:
                 if ukd:
-                    return (g_kd,) + (None,) * 10
+                    return (g_kd,) + (None,) * 11
             elif uce and ukd and g_sum is not None:
-                return (g_sum,) + (None,) * 10
+                return (g_sum,) + (None,) * 11
         if _DUAL[0] is not None:
             # DOT single-pass backward: [go_kd * g_kd ; go_ce * g_ce] stacked,
             # the KD set first (ops/hip_train.py _Dual)
@@ -153,12 +181,12 @@ class _LogitLoss(torch.autograd.Function):
                       g_kd, full[:B], n)
             _ext.call("mda_axpby", _DT[full.dtype], go_ce.float().reshape(1).contiguous(), g_ce,
                       None, g_kd, full[B:], n)
-            return half, None, None, None, None, None, None, None, None, None, None
+            return (half,) + (None,) * 11
         out = torch.empty_like(g_ce)
         a = None if go_ce is None else go_ce.float().reshape(1).contiguous()
         b = None if (go_kd is None or ctx.mode == 0) else go_kd.float().reshape(1).contiguous()
         _ext.call("mda_axpby", _DT[out.dtype], a, g_ce, b, g_kd, out, out.numel())
-        return out, None, None, None, None, None, None, None, None, None, None
+        return (out,) + (None,) * 11
 
 
 def _epoch_ptr(epoch, warmup):
@@ -170,14 +198,27 @@ def _epoch_ptr(epoch, warmup):
     return epoch
 
 
-def ce_kd(logits_s, logits_t, target, temperature, ce_weight, kd_weight):
-    """``(ce_weight * CE(s, y), kd_weight * KD_T(s, t))``."""
+def _check_stand(logit_stand, C):
+    if logit_stand and C < 2:
+        raise ValueError("logit standardisation needs at least 2 classes, got {}".format(C))
+    return bool(logit_stand)
+
+
+def ce_kd(logits_s, logits_t, target, temperature, ce_weight, kd_weight, logit_stand=False):
+    """``(ce_weight * CE(s, y), kd_weight * KD_T(s, t))``.
+
+    ``logit_stand``: the KD term sees the z-scored student and teacher rows
+    (:func:`standardize_logits`); CE stays on the raw logits.
+    """
     C = logits_s.shape[1]
+    logit_stand = _check_stand(logit_stand, C)
     if hip_enabled_for(logits_s) and _supported(logits_s, logits_t, C):
         return _LogitLoss.apply(logits_s, logits_t.detach(), target, 1, 1.0 / float(temperature),
-                                float(ce_weight), float(kd_weight), 0.0, 0.0)
+                                float(ce_weight), float(kd_weight), 0.0, 0.0, None, 0.0,
+                                logit_stand)
     return (ce_weight * cross_entropy(logits_s, target),
-            kd_weight * kd_loss_ref(logits_s, logits_t.detach(), temperature))
+            kd_weight * kd_loss_ref(logits_s, logits_t.detach(), temperature,
+                                    logit_stand=logit_stand))
 
 
 def _warmup(epoch, warmup):
@@ -188,13 +229,16 @@ def _warmup(epoch, warmup):
     return min(float(epoch) / float(warmup), 1.0)
 
 
-def ce_dkd(logits_s, logits_t, target, ce_weight, alpha, beta, temperature, epoch=None, warmup=0):
+def ce_dkd(logits_s, logits_t, target, ce_weight, alpha, beta, temperature, epoch=None, warmup=0,
+           logit_stand=False):
     """``(ce_weight * CE(s, y), min(epoch / warmup, 1) * DKD(s, t))``.
 
     The warm-up factor (``DKD.WARMUP``, reference ``DKD.py:78``) is applied
     inside the fused kernel from the device epoch tensor when one is given.
+    ``logit_stand``: as in :func:`ce_kd`.
     """
     C = logits_s.shape[1]
+    logit_stand = _check_stand(logit_stand, C)
     if (hip_enabled_for(logits_s) and _supported(logits_s, logits_t, C)
             and (epoch is None or isinstance(epoch, torch.Tensor) or not warmup)):
         ep = epoch if isinstance(epoch, torch.Tensor) else None
@@ -202,10 +246,10 @@ def ce_dkd(logits_s, logits_t, target, ce_weight, alpha, beta, temperature, epoc
             ep = ep.to(device=logits_s.device, dtype=torch.float32)
         return _LogitLoss.apply(logits_s, logits_t.detach(), target, 2, 1.0 / float(temperature),
                                 float(ce_weight), 1.0, float(alpha), float(beta), ep,
-                                float(warmup or 0.0) if ep is not None else 0.0)
+                                float(warmup or 0.0) if ep is not None else 0.0, logit_stand)
     return (ce_weight * cross_entropy(logits_s, target),
             _warmup(epoch, warmup) * dkd_loss_ref(logits_s, logits_t.detach(), target, alpha, beta,
-                                                  temperature))
+                                                  temperature, logit_stand=logit_stand))
 
 
 def ce(logits_s, target, ce_weight=1.0):
@@ -215,10 +259,11 @@ def ce(logits_s, target, ce_weight=1.0):
     return ce_weight * cross_entropy(logits_s, target)
 
 
-def kd_loss(logits_student, logits_teacher, temperature):
+def kd_loss(logits_student, logits_teacher, temperature, logit_stand=False):
     return ce_kd(logits_student, logits_teacher, torch.zeros(logits_student.shape[0], dtype=torch.long,
-                 device=logits_student.device), temperature, 0.0, 1.0)[1]
+                 device=logits_student.device), temperature, 0.0, 1.0, logit_stand=logit_stand)[1]
 
 
-def dkd_loss(logits_student, logits_teacher, target, alpha, beta, temperature):
-    return ce_dkd(logits_student, logits_teacher, target, 0.0, alpha, beta, temperature)[1]
+def dkd_loss(logits_student, logits_teacher, target, alpha, beta, temperature, logit_stand=False):
+    return ce_dkd(logits_student, logits_teacher, target, 0.0, alpha, beta, temperature,
+                  logit_stand=logit_stand)[1]
