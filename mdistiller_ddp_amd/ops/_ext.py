@@ -50,10 +50,10 @@ SIGNATURES = {
     "mda_conv_fwd": "pppppppp" + "i" * 15 + "s",
     "mda_conv_plan": "iiipp",
     "mda_conv_set_stamps": "p",
+    "mda_conv_route": "i" * 17 + "p",
     "mda_conv_fwd_bnstats": "ppppp" + "i" * 15 + "p" * 8 + "ff" + "ps",
     "mda_conv_dgrad": "pppp" + "i" * 14 + "s",
     "mda_conv_dgrad_res": "ppppp" + "i" * 14 + "s",
-    "mda_conv_dgrad_bnsum": "ppppp" + "i" * 14 + "ppp" + "i" + "p" + "s",
     "mda_conv_dgrad_bnsum_g": "ppppp" + "i" * 14 + "ppp" + "i" + "p" + "i" + "p" + "ii" + "s",
     "mda_conv_fwd_bnacc_g": "ppppp" + "i" * 14 + "i" + "s",
     "mda_pack_conv_weights_gc": "ppp" + "i" * 7 + "s",
@@ -106,7 +106,6 @@ SIGNATURES = {
     "mda_bn_apply_fin_vr": "ppii" + "ppppp" + "ff" + "p" + "ppp" + "i" + "pppppp" + "ff" + "p" + "s",
     "mda_bn_bwd_fused": "ppppp" + "p" + "iii" + "pp" + "pp" + "ppp" + "ppp" + "p" + "iiii" + "s",
     "mda_bn_bwd_apply_reg": "pppp" + "p" + "iii" + "p" + "pp" + "ppp" + "ppp" + "p" + "iiii" + "s",
-    "mda_conv_fwd_bnacc": "ppppp" + "i" * 14 + "s",
     # CRD memory (csrc/crd.hip)
     "mda_crd_scores": "ppppiiifs",
     "mda_crd_grad": "ppppppiiifs",

@@ -560,7 +560,7 @@ MDA_API int mda_bn_finalize(const float* partial, int64_t nblk, int64_t M, int64
 // (csrc/bnslot.h) instead of partial rows + a finalize launch.
 //
 //   forward   conv (epilogue adds the block's sum y / sum y^2 into the region,
-//             conv_igemm.hip mda_conv_fwd_bnacc)  or  bn_stats_acc_kernel
+//             conv_igemm.hip mda_conv_fwd_bnacc_g)  or  bn_stats_acc_kernel
 //             -> bn_apply_fin_kernel: every block finalizes the channels
 //                from the region in its prologue (block 0 also writes mean /
 //                rstd / scale / shift for the backward and the running stats),
@@ -839,7 +839,7 @@ _Pragma("unroll")
 
 // BN backward whose channel sums a producer already added into the region
 // (the dgrad epilogue of the consuming conv, conv_igemm.hip
-// mda_conv_dgrad_bnsum): one streaming pass (bnbwd.h bn_bwd_apply_body).
+// mda_conv_dgrad_bnsum_g): one streaming pass (bnbwd.h bn_bwd_apply_body).
 template <int V>
 __global__ void __launch_bounds__(256)
 bn_bwd_apply_reg_kernel(BwdArgs a) {
@@ -956,11 +956,7 @@ MDA_API int mda_bn_bwd_fused(const void* dout, const void* dout2, const void* dp
   // small layers hold >= p row iterations per thread on rows_iter / p blocks:
   // a grid barrier over fewer blocks.  MDA_BN_BWD_PER (default 4; measured
   // ShuffleV2 DOT 3.80 -> 3.60 ms, ShuffleV1 3.54 -> 3.48, flagship unchanged)
-  static const int min_per = [] {
-    const char* e = getenv("MDA_BN_BWD_PER");
-    const int v = e ? atoi(e) : 4;
-    return v < 1 ? 1 : (v > 8 ? 8 : v);
-  }();
+  static const int min_per = std::min(std::max((int)mda_env_int("MDA_BN_BWD_PER", 4), 1), 8);
   const int nb = (int)std::min<int64_t>((rows_iter + min_per - 1) / min_per, maxb);
   const int64_t per = (rows_iter + nb - 1) / nb;     // row iterations per thread
   const unsigned ns = (unsigned)nsets;
@@ -982,7 +978,7 @@ MDA_API int mda_bn_bwd_fused(const void* dout, const void* dout2, const void* dp
 }
 
 // BN backward on sums already in `region` (a dgrad epilogue produced them,
-// conv_igemm.hip mda_conv_dgrad_bnsum): one streaming launch.
+// conv_igemm.hip mda_conv_dgrad_bnsum_g): one streaming launch.
 MDA_API int mda_bn_bwd_apply_reg(const void* dout, const void* dpre, const void* y, const void* res,
                                  const float* stats, int64_t M, int64_t C, int64_t act,
                                  void* region, void* dy, void* dres, float* dgamma, float* dbeta,

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define MDA_API extern "C" __attribute__((visibility("default")))
 // status of an optional fused launcher that did not launch (shape / mode not
@@ -53,6 +54,21 @@ __device__ __forceinline__ float wave_max(float v) {
 enum { DT_F32 = 0, DT_BF16 = 1 };
 
 #define MDA_CHECK_LAUNCH() return (int)hipGetLastError()
+
+// Tuning knobs from the environment.  Host functions only (no __device__):
+// kernels take a knob's value as a parameter.  Read each knob once per
+// process, through a function-local static at the place that uses it:
+//   static const bool on = mda_env_flag("MDA_X", true);
+// A flag that defaults on is off only for a value starting with '0'; one that
+// defaults off is on only for a value starting with '1'.
+inline bool mda_env_flag(const char* name, bool default_on) {
+  const char* e = getenv(name);
+  return default_on ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+inline int64_t mda_env_int(const char* name, int64_t dflt) {
+  const char* e = getenv(name);
+  return e ? (int64_t)atoll(e) : dflt;
+}
 
 // ---------------------------------------------------------------------------
 // Deterministic cross-block "last arriver reduces" hand-off (agent-scope

@@ -305,19 +305,10 @@ static int conv1x1_try(const void* x, const void* w, const float* scale, const f
                        int64_t W, int64_t K, int64_t Kp, int64_t Ho, int64_t Wo, int64_t Cout,
                        int64_t stride, int64_t act, hipStream_t st, const FwdApply* fa,
                        int64_t min_m_override) {
-  static const bool on = [] {
-    const char* e = getenv("MDA_CONV1X1_STREAM");
-    return !(e && e[0] == '0');
-  }();
-  static const int64_t min_m = [] {
-    const char* e = getenv("MDA_CONV1X1_MIN_M");
-    return e ? (int64_t)atoll(e) : (int64_t)16384;
-  }();
+  static const bool on = mda_env_flag("MDA_CONV1X1_STREAM", true);
+  static const int64_t min_m = mda_env_int("MDA_CONV1X1_MIN_M", 16384);
   const int64_t M = N * Ho * Wo;
-  static const int cmod = [] {
-    const char* e = getenv("MDA_CONV1X1_C32");  // 0: Cout % 64 only (A/B)
-    return (e && e[0] == '0') ? 64 : 32;
-  }();
+  static const int cmod = mda_env_flag("MDA_CONV1X1_C32", true) ? 32 : 64;  // 0: Cout % 64 only (A/B)
   if (!on || Kp < K || K % 32 || K > 256 || Cout % cmod ||
       M < (min_m_override > 0 ? min_m_override : min_m) || (stride != 1 && stride != 2))
     return -1;

@@ -1587,6 +1587,20 @@ __global__ void __launch_bounds__(256) conv_splitk_epilogue(const ConvParams p, 
   }
 }
 
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// Host launch layer.
+//
+// Every entry point builds the GEMM-view ConvParams (conv_params), asks
+// plan_route which kernel runs it on which grid, and hands the route to
+// launch_route.  plan_route is the one place that validates a launch and
+// chooses the kernel; an entry point that needs a fact about the launch (the
+// per-block partial rows of mda_conv_fwd_bnstats) reads it from the route.
+// mda_conv_route reports the same route without launching anything.
+
+namespace {
+
 // 3x3 / stride 1 / pad 1 "same" conv with Cin % 64 == 0 whose block
 // geometry (see HALO_BM) has a patch of at most `max_rows` rows; fills
 // p.hrows / p.himgs / p.hpb.
@@ -1617,140 +1631,89 @@ bool halo_geometry(ConvParams& p, int max_rows, int cap = HALO_BM) {
   return true;
 }
 
+// Knobs (A/B switches of kernels and heuristics), each read once per process.
 bool halo_eligible(ConvParams& p) {
-  static const bool on = [] {
-    const char* e = getenv("MDA_CONV_HALO");
-    return !(e && e[0] == '0');
-  }();
-  if (!on) return false;
-  return halo_geometry(p, p.Cin == BK ? HALO1_PROWS : HALO_PROWS);
+  static const bool on = mda_env_flag("MDA_CONV_HALO", true);
+  return on && halo_geometry(p, p.Cin == BK ? HALO1_PROWS : HALO_PROWS);
 }
-
-// grouped convs: re-pick the N tile width for the group size (MDA_GROUPED_BN=0: off, A/B)
-bool grouped_bn_fit() {
-  static const bool on = [] {
-    const char* e = getenv("MDA_GROUPED_BN");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-bool use_halo1() {
-  static const bool on = [] {
-    const char* e = getenv("MDA_CONV_HALO1");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// MDA_REG1X1_MIN_M: smallest M of a 1x1 forward conv sent to the register-staged kernel
-int reg1x1_min_m() {
-  static const int v = [] {
-    const char* e = getenv("MDA_REG1X1_MIN_M");
-    return e ? atoi(e) : 32768;
-  }();
-  return v;
-}
-
-bool use_xcd_remap() {
-  static const bool on = [] {
-    const char* e = getenv("MDA_CONV_XCD");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-bool use_krot() {
-  static const bool on = [] {
-    const char* e = getenv("MDA_CONV_KROT");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-bool use_par_dgrad() {
-  static const bool on = [] {
-    const char* e = getenv("MDA_DGRAD_PARITY");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// MDA_HALO_RING: 3 (default) / 8 / 0 (= 8 for grids of <= 320 blocks); the deep
-// ring measured no faster on the CIFAR step (1.295 vs 1.274 ms)
-int halo_ring() {
-  static const int v = [] {
-    const char* e = getenv("MDA_HALO_RING");
-    return e ? atoi(e) : 3;
-  }();
-  return v;
-}
-
+// grouped convs: re-pick the N tile width for the group size
+bool grouped_bn_fit() { static const bool on = mda_env_flag("MDA_GROUPED_BN", true); return on; }
+bool use_halo1() { static const bool on = mda_env_flag("MDA_CONV_HALO1", true); return on; }
+// smallest M of a 1x1 forward conv sent to the register-staged kernel
+int reg1x1_min_m() { static const int v = (int)mda_env_int("MDA_REG1X1_MIN_M", 32768); return v; }
+bool use_xcd_remap() { static const bool on = mda_env_flag("MDA_CONV_XCD", true); return on; }
+bool use_krot() { static const bool on = mda_env_flag("MDA_CONV_KROT", false); return on; }
+bool use_par_dgrad() { static const bool on = mda_env_flag("MDA_DGRAD_PARITY", true); return on; }
 // largest per-block K-step count that takes the single-stage glds variant
-int ring1_max() {
-  static const int v = [] {
-    const char* e = getenv("MDA_GLDS_RING1_MAX");
-    return e ? atoi(e) : 4;
-  }();
-  return v;
+int ring1_max() { static const int v = (int)mda_env_int("MDA_GLDS_RING1_MAX", 4); return v; }
+bool use_glds() { static const bool on = mda_env_flag("MDA_CONV_GLDS", true); return on; }
+
+// loader constants of the glds kernel (XCD order, K rotation, multiply-shift divisors)
+void glds_prep(ConvParams& p) {
+  static const bool perm8_on = mda_env_flag("MDA_HALO_PERM8", true);
+  p.perm8 = perm8_on ? 1 : 0;
+  p.xcd = use_xcd_remap() ? 1 : 0;
+  p.krot = use_krot() ? 1 : 0;
+  make_hdiv((uint32_t)std::max(p.Cin, 1), p.dv_Cin);
+  make_hdiv((uint32_t)std::max(p.KW, 1), p.dv_KW);
+  make_hdiv((uint32_t)std::max(p.Cin / BK, 1), p.dv_cb);
+  make_hdiv((uint32_t)std::max(p.Ho * p.Wo, 1), p.dv_HoWo);
+  make_hdiv((uint32_t)std::max(p.Wo, 1), p.dv_Wo);
+  make_hdiv((uint32_t)std::max(p.stride, 1), p.dv_s);
 }
 
-bool use_glds() {
-  static const bool on = [] {
-    const char* e = getenv("MDA_CONV_GLDS");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+// What plan_route decided: the kernel and its launch geometry.
+enum { K_GLDS = 0, K_REG = 1, K_HALO = 2, K_HALO1 = 3 };
+struct ConvRoute {
+  int rc;         // 0, a hipError_t or MDA_NOT_SERVED; nothing below stream1x1 is valid unless 0
+  int stream1x1;  // the streaming 1x1 kernel (conv1x1.hip) is offered the launch first
+  int family;     // K_*: the kernel that runs when that offer is not made or declined
+  int bm, bn;     // block tile (halo kernels: bm = hpb pixels per block)
+  int mode;       // LOAD_*
+  int ring;       // RING template argument (0: the kernel has none)
+  int flip;       // halo kernels: mirrored taps (stride-1 dgrad)
+  dim3 grid;
+  int steps_per_split, splits;
+  int combine_blocks;  // grid of the split-K combine launch (0: splits == 1)
+};
+
+// Kernel of a route: every instantiation is named exactly once, here.
+using ConvKernel = void (*)(const ConvParams);
+
+template <int BM, int BN, int MODE>
+ConvKernel gemm_kernel(const ConvRoute& r) {
+  if constexpr (MODE != LOAD_SCALAR) {
+    if (r.family == K_GLDS)
+      return r.ring == 1 ? conv_glds_kernel<BM, BN, MODE, 1> : conv_glds_kernel<BM, BN, MODE>;
+  }
+  return conv_fwd_kernel<BM, BN, MODE>;
 }
-
-#define DLAUNCH(K, G, B, S, ST, P) hipLaunchKernelGGL(K, G, B, S, ST, P)
-
 template <int BM, int BN>
-int launch_tile(const ConvParams& p, int mode, int splits, hipStream_t st) {
-  const int ny = p.cout_g < p.Cout ? (p.Cout / p.cout_g) * ((p.cout_g + BN - 1) / BN)
-                                   : (p.Cout + BN - 1) / BN;
-  dim3 grid((p.M + BM - 1) / BM, ny, splits);
-  if (p.cout_g < p.Cout && (mode == LOAD_SCALAR || !use_glds())) return (int)hipErrorInvalidValue;
-  // large-M 1x1 forward convs are output-bandwidth bound: the register-staged
-  // kernel streams them 1.2-1.4x faster than the LDS-DMA one
-  // (profiles/r3_conv1x1_imagenet.md)
-  // (also every short-K one: the CIFAR shortcuts, flagship 0.92-0.93 -> 0.913 ms)
-  const bool reg1x1 = p.KH == 1 && p.KW == 1 && p.cout_g >= p.Cout &&
-                      (p.M >= reg1x1_min_m() || p.Kp <= 4 * BK) &&
-                      (mode == LOAD_FAST || mode == LOAD_VEC8);
-  if (mode != LOAD_SCALAR && use_glds() && !reg1x1 && p.steps_per_split <= ring1_max()) {  // short-K blocks
-    if (mode == LOAD_FAST)
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_FAST, 1>), grid, dim3(256), 0, st, p);
-    else if (mode == LOAD_VEC8)
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_VEC8, 1>), grid, dim3(256), 0, st, p);
-    else if (mode == LOAD_DGRAD_FAST)
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_DGRAD_FAST, 1>), grid, dim3(256), 0, st, p);
-    else
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_DGRAD_VEC8, 1>), grid, dim3(256), 0, st, p);
-    return (int)hipGetLastError();
+ConvKernel gemm_kernel(const ConvRoute& r) {
+  switch (r.mode) {
+    case LOAD_FAST: return gemm_kernel<BM, BN, LOAD_FAST>(r);
+    case LOAD_VEC8: return gemm_kernel<BM, BN, LOAD_VEC8>(r);
+    case LOAD_DGRAD_FAST: return gemm_kernel<BM, BN, LOAD_DGRAD_FAST>(r);
+    case LOAD_DGRAD_VEC8: return gemm_kernel<BM, BN, LOAD_DGRAD_VEC8>(r);
+    default: return gemm_kernel<BM, BN, LOAD_SCALAR>(r);
   }
-  if (mode != LOAD_SCALAR && use_glds() && !reg1x1) {
-    if (mode == LOAD_FAST)
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_FAST>), grid, dim3(256), 0, st, p);
-    else if (mode == LOAD_VEC8)
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_VEC8>), grid, dim3(256), 0, st, p);
-    else if (mode == LOAD_DGRAD_FAST)
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p);
-    else
-      DLAUNCH((conv_glds_kernel<BM, BN, LOAD_DGRAD_VEC8>), grid, dim3(256), 0, st, p);
-    return (int)hipGetLastError();
+}
+template <int BN>
+ConvKernel halo_kernel(const ConvRoute& r) {
+  if (r.family == K_HALO1) return r.flip ? conv_halo1_kernel<BN, true> : conv_halo1_kernel<BN, false>;
+  return r.flip ? conv_halo_kernel<BN, true> : conv_halo_kernel<BN, false>;
+}
+ConvKernel route_kernel(const ConvRoute& r) {
+  if (r.family == K_HALO || r.family == K_HALO1) return r.bn == 32 ? halo_kernel<32>(r) : halo_kernel<64>(r);
+  switch (r.bm * 1000 + r.bn) {
+    case 128128: return gemm_kernel<128, 128>(r);
+    case 128064: return gemm_kernel<128, 64>(r);
+    case 128032: return gemm_kernel<128, 32>(r);
+    case 64128: return gemm_kernel<64, 128>(r);
+    case 64064: return gemm_kernel<64, 64>(r);
+    case 64032: return gemm_kernel<64, 32>(r);
+    default: return nullptr;  // plan_route admits no other tile
   }
-  if (mode == LOAD_FAST)
-    DLAUNCH((conv_fwd_kernel<BM, BN, LOAD_FAST>), grid, dim3(256), 0, st, p);
-  else if (mode == LOAD_VEC8)
-    DLAUNCH((conv_fwd_kernel<BM, BN, LOAD_VEC8>), grid, dim3(256), 0, st, p);
-  else if (mode == LOAD_DGRAD_FAST)
-    DLAUNCH((conv_fwd_kernel<BM, BN, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p);
-  else if (mode == LOAD_DGRAD_VEC8)
-    DLAUNCH((conv_fwd_kernel<BM, BN, LOAD_DGRAD_VEC8>), grid, dim3(256), 0, st, p);
-  else
-    DLAUNCH((conv_fwd_kernel<BM, BN, LOAD_SCALAR>), grid, dim3(256), 0, st, p);
-  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -1767,11 +1730,9 @@ MDA_API int mda_conv_set_stamps(void* buf) {
 // Host-side tile / split-K choice (also used by Python to size the workspace).
 // Returns tile code BM*1000+BN in *tile and the split count in *splits.
 MDA_API int mda_conv_plan(int64_t M, int64_t Cout, int64_t Kp, int64_t* tile, int64_t* splits) {
-  // >= 1 workgroup per CU on 256 CUs before splitting K (MDA_CONV_TARGET overrides)
-  static const int64_t target = [] {
-    const char* e = getenv("MDA_CONV_TARGET");
-    return e ? (int64_t)atoi(e) : (int64_t)256;  // A/B: profiles/r2_conv_target_ab.md
-  }();
+  // >= 1 workgroup per CU on 256 CUs before splitting K (MDA_CONV_TARGET
+  // overrides; A/B: profiles/r2_conv_target_ab.md)
+  static const int64_t target = (int)mda_env_int("MDA_CONV_TARGET", 256);
   int bn = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : 128);
   int bm = 128;
   auto blocks = [&](int bm_, int bn_) { return ((M + bm_ - 1) / bm_) * ((Cout + bn_ - 1) / bn_); };
@@ -1795,56 +1756,63 @@ extern "C" int mda_conv1x1_stream_try(const void* x, const void* w, const float*
 
 namespace {
 
-// loader constants of the glds kernel (XCD order, K rotation, multiply-shift divisors)
-void glds_prep(ConvParams& p) {
-  static const int perm8_on = [] {
-    const char* e = getenv("MDA_HALO_PERM8");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  p.perm8 = perm8_on;
-  p.xcd = use_xcd_remap() ? 1 : 0;
-  p.krot = use_krot() ? 1 : 0;
-  make_hdiv((uint32_t)std::max(p.Cin, 1), p.dv_Cin);
-  make_hdiv((uint32_t)std::max(p.KW, 1), p.dv_KW);
-  make_hdiv((uint32_t)std::max(p.Cin / BK, 1), p.dv_cb);
-  make_hdiv((uint32_t)std::max(p.Ho * p.Wo, 1), p.dv_HoWo);
-  make_hdiv((uint32_t)std::max(p.Wo, 1), p.dv_Wo);
-  make_hdiv((uint32_t)std::max(p.stride, 1), p.dv_s);
+// GEMM view of a dense conv of x [N, H, W, Cin] with w [Cout][Kp] into y
+// [N, Ho, Wo, Cout]: what every entry point starts from.  Epilogue operands,
+// grouping (ldx, cout_g) and the dgrad extras are set by the caller.
+ConvParams conv_params(const void* x, const void* w, void* y, float* partial, int64_t N, int64_t H,
+                       int64_t W, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH,
+                       int64_t KW, int64_t stride, int64_t pad, int64_t Kp) {
+  ConvParams p{};
+  p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.y = (bf16_t*)y; p.partial = partial;
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.KH = KH;
+  p.KW = KW; p.stride = stride; p.pad = pad; p.K = KH * KW * Cin; p.Kp = Kp; p.M = N * Ho * Wo;
+  p.zsplits = 1;
+  p.stamps = g_stamps;
+  return p;
 }
 
-int dispatch(ConvParams& p, int mode, int64_t tile, int64_t splits, hipStream_t st, int halo = 0) {
-  if (p.Kp % BK || p.Kp < p.K) return (int)hipErrorInvalidValue;
+int fwd_mode(int64_t Cin) {
+  return (Cin % BK == 0) ? LOAD_FAST : (Cin % 8 == 0 ? LOAD_VEC8 : LOAD_SCALAR);
+}
+
+// Validates the launch of p and chooses its kernel and grid; fills the
+// launch-derived fields of p (loader constants, buffer ranges, K-steps per
+// split, parity splits).  Launches nothing.  tile / splits: 0 = mda_conv_plan;
+// halo: 0 = not eligible, 1 = halo_eligible(p), 2 = the same with mirrored taps.
+ConvRoute plan_route(ConvParams& p, int mode, int64_t tile, int64_t splits, int halo) {
+  ConvRoute r{};
+  r.rc = (int)hipErrorInvalidValue;  // until the plan is complete
+  r.mode = mode;
+  if (p.Kp % BK || p.Kp < p.K) return r;
   if (p.ldx <= 0) p.ldx = p.Cin;
   if (p.cout_g <= 0) p.cout_g = p.Cout;
+  const bool grouped = p.cout_g < p.Cout;
   // memory-bound 1x1 convs (and stride-1 1x1 dgrads): the streaming kernel
   // (conv1x1.hip) -- transposed MFMA, resident weights, stores straight from
-  // the accumulators; -1 = shape not served, fall through
-  if (p.KH == 1 && p.KW == 1 && p.pad == 0 && p.cout_g >= p.Cout && p.ldx == p.Cin &&
-      p.bnb_slot == nullptr && p.stats_part == nullptr && p.stamps == nullptr &&
-      (mode == LOAD_FAST || mode == LOAD_VEC8 ||
-       ((mode == LOAD_DGRAD_FAST || mode == LOAD_DGRAD_VEC8) && p.stride == 1))) {
-    // (K = Cin a multiple of 32 is enough there: LOAD_VEC8 covers K = 32 / 96 / ...)
-    const bool fwd = mode == LOAD_FAST || mode == LOAD_VEC8;
-    const int rc = mda_conv1x1_stream_try(p.x, p.w, p.scale, p.bias, p.res, p.y, p.preact,
-                                          p.stats_slot, p.N, p.H, p.W, p.Cin, p.Kp, p.Ho, p.Wo,
-                                          p.Cout, fwd ? p.stride : 1, p.act, st);
-    if (rc != -1) return rc;
-  }
+  // the accumulators -- is asked first, whatever the rest of the plan says
+  // (K = Cin a multiple of 32 is enough there: LOAD_VEC8 covers K = 32 / 96 / ...)
+  r.stream1x1 = p.KH == 1 && p.KW == 1 && p.pad == 0 && !grouped && p.ldx == p.Cin &&
+                p.bnb_slot == nullptr && p.stats_part == nullptr && p.stamps == nullptr &&
+                (mode == LOAD_FAST || mode == LOAD_VEC8 ||
+                 ((mode == LOAD_DGRAD_FAST || mode == LOAD_DGRAD_VEC8) && p.stride == 1));
   glds_prep(p);
-  if (p.cout_g < p.Cout) {  // grouped: group-aligned tiles on the glds kernel only
+  if (grouped) {  // group-aligned tiles on the glds kernel only
     if (p.Cout % p.cout_g || p.ldx != p.Cin * (p.Cout / p.cout_g) || p.cout_g % 8 || p.Cin % 8)
-      return (int)hipErrorInvalidValue;
+      return r;
     halo = 0;
     p.par = 0;
   }
   const int64_t xb = (int64_t)p.N * p.H * p.W * p.ldx * 2, wb = (int64_t)p.Cout * p.Kp * 2;
-  if (xb >= ((int64_t)1 << 31) || wb >= ((int64_t)1 << 31) || (int64_t)p.M * p.Cout >= ((int64_t)1 << 31))
-    return (int)hipErrorInvalidValue;  // 32-bit buffer offsets
+  // 32-bit buffer offsets.  An oversized launch is an error, but its geometry
+  // is still planned: mda_conv_fwd_bnstats decides from it whether the
+  // streaming offer above stands
+  const bool oversized = xb >= ((int64_t)1 << 31) || wb >= ((int64_t)1 << 31) ||
+                         (int64_t)p.M * p.Cout >= ((int64_t)1 << 31);
   p.x_bytes = (int)xb;
   p.w_bytes = (int)wb;
   if (tile == 0 || splits == 0) mda_conv_plan(p.M, p.Cout, p.Kp, &tile, &splits);
-  if (splits > 1 && p.partial == nullptr) return (int)hipErrorInvalidValue;
-  if (p.cout_g < p.Cout && grouped_bn_fit()) {
+  if (splits > 1 && p.partial == nullptr) return r;
+  if (grouped && grouped_bn_fit()) {
     // group-aligned N tiles: the tile width that pads a group least (the
     // plan's width is chosen for the whole Cout).  ShuffleNetV1's groups of
     // 24 / 72 / 80 / 160 channels waste 25-62 % of a 64 / 128-wide tile.
@@ -1857,97 +1825,232 @@ int dispatch(ConvParams& p, int mode, int64_t tile, int64_t splits, hipStream_t 
     }
     tile = tile / 1000 * 1000 + best;
   }
-  int rc;
   if (p.x2 != nullptr && (halo || p.par <= 1 || splits != 1 || p.cin2 % BK || p.cls2 < 0 ||
-                          p.cls2 >= p.par * p.par))
-    return MDA_NOT_SERVED;  // a folded 1 x 1 conv needs the strided (parity) glds path
-  if (halo) {
-    const int nchunks = p.Cin / BK;
-    // the multi-chunk kernel double-buffers patches of at most HALO_PROWS rows
-    if (!(nchunks == 1 && splits == 1 && use_halo1()) &&
-        p.himgs * (p.hrows + 2) * (p.W + 2) > HALO_PROWS)
-      halo = 0;
+                          p.cls2 >= p.par * p.par)) {
+    // a folded 1 x 1 conv needs the strided (parity) glds path
+    if (!oversized) r.rc = MDA_NOT_SERVED;
+    return r;
   }
-  if (halo) {  // halo kernel: split over 64-channel chunks, hpb pixels per block
-    const int nchunks = p.Cin / BK;
-    p.steps_per_split = (int)((nchunks + splits - 1) / splits);
+  const int nchunks = p.Cin / BK;
+  const bool halo1 = nchunks == 1 && splits == 1 && use_halo1();
+  // the multi-chunk halo kernel double-buffers patches of at most HALO_PROWS
+  // rows: a larger patch (halo1 geometry, Cin = 64) runs the glds kernel
+  if (halo && !halo1 && p.himgs * (p.hrows + 2) * (p.W + 2) > HALO_PROWS) halo = 0;
+  int steps;
+  if (halo) {  // split over 64-channel chunks, hpb pixels per block
     // (halving the channel tile of 8x8 convs with fewer blocks than CUs helped
     // the student alone but not beside the look-ahead teacher: deleted in
     // round 6, profiles/r6_ab.md)
-    const int bn = p.Cout <= 32 ? 32 : 64;
-    dim3 grid((p.M + p.hpb - 1) / p.hpb, (p.Cout + bn - 1) / bn, (int)splits);
-    if (nchunks == 1 && splits == 1 && use_halo1()) {
-      if (bn == 32) {
-        if (halo == 2) DLAUNCH((conv_halo1_kernel<32, true>), grid, dim3(256), 0, st, p);
-        else DLAUNCH((conv_halo1_kernel<32, false>), grid, dim3(256), 0, st, p);
-      } else {
-        if (halo == 2) DLAUNCH((conv_halo1_kernel<64, true>), grid, dim3(256), 0, st, p);
-        else DLAUNCH((conv_halo1_kernel<64, false>), grid, dim3(256), 0, st, p);
-      }
-    } else {
-      const int64_t nblocks = (int64_t)grid.x * grid.y * grid.z;
-      const bool deep = halo_ring() == 8 || (halo_ring() == 0 && nblocks <= 320);
-      if (bn == 32) {
-        if (deep) {
-          if (halo == 2) DLAUNCH((conv_halo_kernel<32, true, 8>), grid, dim3(256), 0, st, p);
-          else DLAUNCH((conv_halo_kernel<32, false, 8>), grid, dim3(256), 0, st, p);
-        } else {
-          if (halo == 2) DLAUNCH((conv_halo_kernel<32, true>), grid, dim3(256), 0, st, p);
-          else DLAUNCH((conv_halo_kernel<32, false>), grid, dim3(256), 0, st, p);
-        }
-      } else {
-        if (deep) {
-          if (halo == 2) DLAUNCH((conv_halo_kernel<64, true, 8>), grid, dim3(256), 0, st, p);
-          else DLAUNCH((conv_halo_kernel<64, false, 8>), grid, dim3(256), 0, st, p);
-        } else {
-          if (halo == 2) DLAUNCH((conv_halo_kernel<64, true>), grid, dim3(256), 0, st, p);
-          else DLAUNCH((conv_halo_kernel<64, false>), grid, dim3(256), 0, st, p);
-        }
-      }
-    }
-    rc = (int)hipGetLastError();
-  } else if (p.par > 1) {
-    // strided dgrad by parity class (glds kernel, Cout % 64 == 0 only)
-    const int s2 = p.par * p.par;
-    int steps = ((p.KH + p.par - 1) / p.par) * ((p.KW + p.par - 1) / p.par) * (p.Cin / BK);
-    if (p.x2 != nullptr) {  // the folded 1 x 1 conv's class: its own taps + cin2 / 64
-      const ParClass c = par_class(p, p.cls2);
-      steps = std::max(steps, c.nkh * c.nkw * (p.Cin / BK) + p.cin2 / BK);
-    }
-    p.zsplits = (int)splits;
-    p.steps_per_split = (int)((steps + splits - 1) / splits);
-    const int bm = (int)(tile / 1000), bn = (int)(tile % 1000);
-    const int mc = p.N * ((p.Ho + p.par - 1) / p.par) * ((p.Wo + p.par - 1) / p.par);
-    dim3 grid((mc + bm - 1) / bm, (p.Cout + bn - 1) / bn, s2 * (int)splits);
-    switch (tile) {
-      case 128128: DLAUNCH((conv_glds_kernel<128, 128, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p); break;
-      case 128064: DLAUNCH((conv_glds_kernel<128, 64, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p); break;
-      case 128032: DLAUNCH((conv_glds_kernel<128, 32, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p); break;
-      case 64128: DLAUNCH((conv_glds_kernel<64, 128, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p); break;
-      case 64064: DLAUNCH((conv_glds_kernel<64, 64, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p); break;
-      case 64032: DLAUNCH((conv_glds_kernel<64, 32, LOAD_DGRAD_FAST>), grid, dim3(256), 0, st, p); break;
-      default: return (int)hipErrorInvalidValue;
-    }
-    rc = (int)hipGetLastError();
+    r.family = halo1 ? K_HALO1 : K_HALO;
+    r.bm = p.hpb;
+    r.bn = p.Cout <= 32 ? 32 : 64;
+    r.ring = halo1 ? 0 : 3;
+    r.flip = halo == 2;
+    steps = nchunks;
+    r.grid = dim3((p.M + r.bm - 1) / r.bm, (p.Cout + r.bn - 1) / r.bn, (int)splits);
   } else {
-  const int steps = p.Kp / BK;
-  p.steps_per_split = (int)((steps + splits - 1) / splits);
-  switch (tile) {
-    case 128128: rc = launch_tile<128, 128>(p, mode, splits, st); break;
-    case 128064: rc = launch_tile<128, 64>(p, mode, splits, st); break;
-    case 128032: rc = launch_tile<128, 32>(p, mode, splits, st); break;
-    case 64128: rc = launch_tile<64, 128>(p, mode, splits, st); break;
-    case 64064: rc = launch_tile<64, 64>(p, mode, splits, st); break;
-    case 64032: rc = launch_tile<64, 32>(p, mode, splits, st); break;
-    default: return (int)hipErrorInvalidValue;
+    r.bm = (int)(tile / 1000);
+    r.bn = (int)(tile % 1000);
+    if ((r.bm != 64 && r.bm != 128) || (r.bn != 32 && r.bn != 64 && r.bn != 128)) return r;
+    if (p.par > 1) {
+      // strided dgrad by parity class (glds kernel, Cout % 64 == 0 only)
+      steps = ((p.KH + p.par - 1) / p.par) * ((p.KW + p.par - 1) / p.par) * nchunks;
+      if (p.x2 != nullptr) {  // the folded 1 x 1 conv's class: its own taps + cin2 / 64
+        const ParClass c = par_class(p, p.cls2);
+        steps = std::max(steps, c.nkh * c.nkw * nchunks + p.cin2 / BK);
+      }
+      p.zsplits = (int)splits;
+      const int mc = p.N * ((p.Ho + p.par - 1) / p.par) * ((p.Wo + p.par - 1) / p.par);
+      r.family = K_GLDS;
+      r.ring = GLDS_NBUF;
+      r.grid = dim3((mc + r.bm - 1) / r.bm, (p.Cout + r.bn - 1) / r.bn, p.par * p.par * (int)splits);
+    } else {
+      if (grouped && (mode == LOAD_SCALAR || !use_glds())) return r;
+      steps = p.Kp / BK;
+      // large-M 1x1 forward convs are output-bandwidth bound: the register-staged
+      // kernel streams them 1.2-1.4x faster than the LDS-DMA one
+      // (profiles/r3_conv1x1_imagenet.md)
+      // (also every short-K one: the CIFAR shortcuts, flagship 0.92-0.93 -> 0.913 ms)
+      const bool reg1x1 = p.KH == 1 && p.KW == 1 && !grouped &&
+                          (p.M >= reg1x1_min_m() || p.Kp <= 4 * BK) &&
+                          (mode == LOAD_FAST || mode == LOAD_VEC8);
+      r.family = (mode != LOAD_SCALAR && use_glds() && !reg1x1) ? K_GLDS : K_REG;
+      if (r.family == K_GLDS)  // short-K blocks: the single-stage variant
+        r.ring = (steps + splits - 1) / splits <= ring1_max() ? 1 : GLDS_NBUF;
+      const int tiles_n = (p.cout_g + r.bn - 1) / r.bn;  // per group
+      r.grid = dim3((p.M + r.bm - 1) / r.bm, (p.Cout / p.cout_g) * tiles_n, (int)splits);
+    }
   }
+  r.splits = (int)splits;
+  p.steps_per_split = r.steps_per_split = (int)((steps + splits - 1) / splits);
+  if (splits > 1) {
+    const int64_t total = (int64_t)p.M * p.Cout;
+    r.combine_blocks = (int)std::min<int64_t>(((p.Cout % 8 == 0 ? total / 8 : total) + 255) / 256, 2048);
   }
-  if (rc || splits <= 1) return rc;
-  int64_t total = (int64_t)p.M * p.Cout;
-  int64_t work = (p.Cout % 8 == 0) ? total / 8 : total;
-  int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-  hipLaunchKernelGGL(conv_splitk_epilogue, dim3(blocks), dim3(256), 0, st, p, (int)splits);
+  if (!oversized) r.rc = 0;
+  return r;
+}
+
+int launch_route(const ConvParams& p, const ConvRoute& r, hipStream_t st) {
+  if (r.stream1x1) {  // -1 = shape not served there: run the route
+    const bool fwd = r.mode == LOAD_FAST || r.mode == LOAD_VEC8;
+    const int rc = mda_conv1x1_stream_try(p.x, p.w, p.scale, p.bias, p.res, p.y, p.preact,
+                                          p.stats_slot, p.N, p.H, p.W, p.Cin, p.Kp, p.Ho, p.Wo,
+                                          p.Cout, fwd ? p.stride : 1, p.act, st);
+    if (rc != -1) return rc;
+  }
+  if (r.rc) return r.rc;
+  hipLaunchKernelGGL(route_kernel(r), r.grid, dim3(256), 0, st, p);
+  const int rc = (int)hipGetLastError();
+  if (rc || r.splits <= 1) return rc;
+  hipLaunchKernelGGL(conv_splitk_epilogue, dim3(r.combine_blocks), dim3(256), 0, st, p, r.splits);
   return (int)hipGetLastError();
+}
+
+// One planned launch: the parameters and their route.  Each entry point has a
+// planner that builds it (a refused call carries only a status); the entry
+// point launches it, mda_conv_route reports it.
+struct ConvCall {
+  ConvParams p;
+  ConvRoute r;
+};
+
+ConvCall refused(int rc) {
+  ConvCall c{};
+  c.r.rc = rc;
+  return c;
+}
+
+int launch(const ConvCall& c, hipStream_t st) { return launch_route(c.p, c.r, st); }
+
+// mda_conv_fwd; the caller adds the epilogue operands, which no route depends on
+ConvCall plan_fwd(const void* x, const void* w, void* y, float* partial, int64_t N, int64_t H,
+                  int64_t W, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH,
+                  int64_t KW, int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
+                  int64_t splits) {
+  ConvCall c{};
+  c.p = conv_params(x, w, y, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp);
+  c.r = plan_route(c.p, fwd_mode(Cin), tile, splits, halo_eligible(c.p) ? 1 : 0);
+  return c;
+}
+
+// mda_conv_fwd_bnstats: *fused = the conv's epilogue writes the per-block
+// statistics partials (r.grid.x rows of them) into bn_partial
+ConvCall plan_fwd_bnstats(const void* x, const void* w, void* y, float* partial, float* bn_partial,
+                          int64_t bn_partial_cap, int64_t N, int64_t H, int64_t W, int64_t Cin,
+                          int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
+                          int64_t stride, int64_t pad, int64_t Kp, int64_t tile, int64_t splits,
+                          bool* fused) {
+  *fused = false;
+  if (Cout % 8 || Cout > 2048) return refused((int)hipErrorInvalidValue);
+  ConvCall c = plan_fwd(x, w, y, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp,
+                        tile, splits);
+  // one row of partials per M-block of the launch that runs (also planned for
+  // an oversized conv, whose status is an error); the streaming 1x1 kernel
+  // writes none, so a fused launch is not offered to it
+  *fused = c.r.splits == 1 && (int64_t)c.r.grid.x * 2 * Cout <= bn_partial_cap;
+  if (*fused) {
+    c.p.stats_part = bn_partial;
+    c.r.stream1x1 = 0;
+  }
+  return c;
+}
+
+// mda_conv_fwd_bnacc_g
+ConvCall plan_fwd_bnacc(const void* x, const void* w, void* y, float* partial, void* region,
+                        int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Ho, int64_t Wo,
+                        int64_t Cout, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
+                        int64_t Kp, int64_t tile, int64_t splits, int64_t groups) {
+  if (groups < 1 || Cin % groups || Cout % groups) return refused((int)hipErrorInvalidValue);
+  if (Cout % 8 || Cout > SLOT_CMAX) return refused((int)hipErrorInvalidValue);
+  ConvCall c{};
+  ConvParams& p = c.p;
+  p = conv_params(x, w, y, partial, N, H, W, Cin / groups, Ho, Wo, Cout, KH, KW, stride, pad, Kp);
+  p.ldx = (int)Cin;
+  p.cout_g = (int)(Cout / groups);
+  const int mode = fwd_mode(p.Cin);
+  if (groups > 1 && mode == LOAD_SCALAR) return refused((int)hipErrorInvalidValue);
+  if (tile == 0 || splits == 0) mda_conv_plan(p.M, p.Cout, p.Kp, &tile, &splits);
+  if (splits == 1) p.stats_slot = (BnRegion*)region;
+  c.r = plan_route(p, mode, tile, splits, (groups == 1 && halo_eligible(p)) ? 1 : 0);
+  return c;
+}
+
+// Input gradient of a convolution (any stride): dx[N, H, W, Cin] =
+// sum_{kh,kw,co} dy[N, (ih+pad-kh)/s, (iw+pad-kw)/s, co] * w[co, ci, kh, kw].
+// wt: weights packed [Cin][Kp] with k = (kh*KW + kw)*Cout + co (mda_pack_conv_weights).
+// dy: [N, Ho, Wo, Cout]; requires Cout % 8 == 0.  The exported variants below
+// say what res, bn_*, region, groups and x2 / w2 add.
+ConvCall plan_dgrad(const void* dy, const void* wt, void* dx, float* partial, const void* res,
+                    int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Ho, int64_t Wo,
+                    int64_t Cout, int64_t KH, int64_t KW, int64_t stride, int64_t pad, int64_t Kp,
+                    int64_t tile, int64_t splits, const void* bn_y, const void* bn_res,
+                    const float* bn_stats, int64_t bn_act, void* region, int64_t groups,
+                    const float* bn_vres, int64_t bn_mh, int64_t bn_rstride, const void* x2,
+                    const void* w2, int64_t cin2, int64_t kp2) {
+  if (Cout % 8 || groups < 1 || Cin % groups || Cout % groups)
+    return refused((int)hipErrorInvalidValue);
+  if (region != nullptr && (splits != 1 || Cin % 8 || Cin > SLOT_CMAX || bn_y == nullptr ||
+                            bn_stats == nullptr))
+    return refused((int)hipErrorInvalidValue);
+  // two stacked sets: dx rows [mh, 2 mh) are set 1 (N holds both sets' images)
+  if (bn_mh != 0 && (region == nullptr || bn_mh * 2 != N * H * W || bn_rstride <= 0))
+    return refused((int)hipErrorInvalidValue);
+  // GEMM view: rows = dx pixels, cols = Cin, k = (tap, co); "input" image = dy
+  ConvCall c{};
+  ConvParams& p = c.p;
+  p = conv_params(dy, wt, dx, partial, N, Ho, Wo, Cout / groups, H, W, Cin, KH, KW, stride, pad, Kp);
+  p.res = (const bf16_t*)res;
+  p.ldx = (int)Cout;
+  p.cout_g = (int)(Cin / groups);
+  p.bnb_mh = (int)bn_mh;
+  p.bnb_rstride = bn_rstride;
+  p.bnb_y = (const bf16_t*)bn_y;
+  p.bnb_res = (const bf16_t*)bn_res;
+  p.bnb_stats = bn_stats;
+  p.bnb_slot = (BnRegion*)region;
+  p.bnb_act = (int)bn_act;
+  p.bnb_vres = bn_res != nullptr ? bn_vres : nullptr;
+  p.x2 = (const bf16_t*)x2;
+  p.w2 = (const bf16_t*)w2;
+  p.cin2 = (int)cin2;
+  p.kp2 = (int)kp2;
+  p.cls2 = -1;
+  const int mode = (p.Cin % BK == 0) ? LOAD_DGRAD_FAST : LOAD_DGRAD_VEC8;
+  // strided dgrad: one GEMM per output-parity class with only its taps
+  if (stride > 1 && mode == LOAD_DGRAD_FAST && use_glds() && use_par_dgrad() && groups == 1)
+    p.par = (int)stride;
+  if (x2 != nullptr) {
+    if (p.par <= 1 || groups != 1 || bn_mh != 0) return refused(MDA_NOT_SERVED);
+    // the 1 x 1 / stride-s / pad-0 conv samples dx pixels (s i, s j): parity
+    // class (pad mod s, pad mod s), whose dy pixel minus pad / s is (i, j)
+    const int ph = (int)(pad % stride);
+    p.cls2 = ph * (int)stride + ph;
+    p.sh2 = (int)(pad / stride);
+    if (tile == 0 || splits == 0) mda_conv_plan(p.M, p.Cout, p.Kp, &tile, &splits);
+    if (splits != 1) return refused(MDA_NOT_SERVED);
+  }
+  if (groups > 1 && (p.Cin % 8 || p.cout_g % 8)) return refused((int)hipErrorInvalidValue);
+  // stride-1 3x3 pad-1 dgrad is a "same" conv of dy with the mirrored taps
+  c.r = plan_route(p, mode, tile, splits, (groups == 1 && halo_eligible(p)) ? 2 : 0);
+  return c;
+}
+
+// mda_conv_dgrad_bnsum2
+ConvCall plan_dgrad_pair(const void* dy, const void* wt, void* dx, int64_t N, int64_t H, int64_t W,
+                         int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
+                         int64_t stride, int64_t pad, int64_t Kp, const void* bn_y,
+                         const void* bn_res, const float* bn_stats, int64_t bn_act, void* region,
+                         const float* bn_vres, const void* dy2, const void* wt2, int64_t cin2,
+                         int64_t kp2) {
+  if (dy2 == nullptr || wt2 == nullptr || cin2 <= 0 || cin2 % BK || kp2 < cin2 || kp2 % BK)
+    return refused(MDA_NOT_SERVED);
+  int64_t tile = 0, splits = 0;
+  mda_conv_plan(N * H * W, Cin, Kp, &tile, &splits);
+  if (splits != 1) return refused(MDA_NOT_SERVED);
+  return plan_dgrad(dy, wt, dx, nullptr, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad,
+                    Kp, tile, splits, bn_y, bn_res, bn_stats, bn_act, region, 1, bn_vres, 0, 0, dy2,
+                    wt2, cin2, kp2);
 }
 
 }  // namespace
@@ -1959,53 +2062,23 @@ MDA_API int mda_conv_fwd(const void* x, const void* w, const float* scale, const
                          int64_t H, int64_t W, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
                          int64_t KH, int64_t KW, int64_t stride, int64_t pad, int64_t Kp,
                          int64_t act, int64_t tile, int64_t splits, hipStream_t st) {
-  ConvParams p{};
-  p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = scale; p.bias = bias;
-  p.res = (const bf16_t*)res; p.y = (bf16_t*)y; p.preact = (bf16_t*)preact; p.partial = partial;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.KH = KH;
-  p.KW = KW; p.stride = stride; p.pad = pad; p.K = KH * KW * Cin; p.Kp = Kp; p.M = N * Ho * Wo;
-  p.act = act;
-  p.par = 0;
-  p.zsplits = 1;
-  p.stats_part = nullptr;
-  p.stats_slot = nullptr;
-  p.stamps = g_stamps;
-  int mode = (Cin % BK == 0) ? LOAD_FAST : (Cin % 8 == 0 ? LOAD_VEC8 : LOAD_SCALAR);
-  return dispatch(p, mode, tile, splits, st, halo_eligible(p) ? 1 : 0);
+  ConvCall c = plan_fwd(x, w, y, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp,
+                        tile, splits);
+  c.p.scale = scale;
+  c.p.bias = bias;
+  c.p.res = (const bf16_t*)res;
+  c.p.preact = (bf16_t*)preact;
+  c.p.act = act;
+  return launch(c, st);
 }
-
-// Input gradient of a convolution (any stride): dx[N, H, W, Cin] =
-// sum_{kh,kw,co} dy[N, (ih+pad-kh)/s, (iw+pad-kw)/s, co] * w[co, ci, kh, kw].
-// wt: weights packed [Cin][Kp] with k = (kh*KW + kw)*Cout + co (mda_pack_conv_weights).
-// dy: [N, Ho, Wo, Cout]; requires Cout % 8 == 0.
-MDA_API int mda_conv_dgrad_res(const void* dy, const void* wt, void* dx, float* partial,
-                               const void* res, int64_t N, int64_t H, int64_t W, int64_t Cin,
-                               int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
-                               int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
-                               int64_t splits, hipStream_t st);
-
-MDA_API int mda_conv_dgrad_bnsum(const void* dy, const void* wt, void* dx, float* partial,
-                                 const void* res, int64_t N, int64_t H, int64_t W, int64_t Cin,
-                                 int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
-                                 int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
-                                 int64_t splits, const void* bn_y, const void* bn_res,
-                                 const float* bn_stats, int64_t bn_act, void* region,
-                                 hipStream_t st);
-MDA_API int mda_conv_dgrad_bnsum_g(const void* dy, const void* wt, void* dx, float* partial,
-                                   const void* res, int64_t N, int64_t H, int64_t W, int64_t Cin,
-                                   int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
-                                   int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
-                                   int64_t splits, const void* bn_y, const void* bn_res,
-                                   const float* bn_stats, int64_t bn_act, void* region,
-                                   int64_t groups, const float* bn_vres, int64_t bn_mh,
-                                   int64_t bn_rstride, hipStream_t st);
 
 MDA_API int mda_conv_dgrad(const void* dy, const void* wt, void* dx, float* partial, int64_t N,
                            int64_t H, int64_t W, int64_t Cin, int64_t Ho, int64_t Wo,
                            int64_t Cout, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
                            int64_t Kp, int64_t tile, int64_t splits, hipStream_t st) {
-  return mda_conv_dgrad_res(dy, wt, dx, partial, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW,
-                            stride, pad, Kp, tile, splits, st);
+  return launch(plan_dgrad(dy, wt, dx, partial, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW,
+                           stride, pad, Kp, tile, splits, nullptr, nullptr, nullptr, 0, nullptr, 1,
+                           nullptr, 0, 0, nullptr, nullptr, 0, 0), st);
 }
 
 // dx = dgrad(dy) (+ res): the residual-add epilogue sums the gradient another
@@ -2016,8 +2089,9 @@ MDA_API int mda_conv_dgrad_res(const void* dy, const void* wt, void* dx, float* 
                                int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
                                int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
                                int64_t splits, hipStream_t st) {
-  return mda_conv_dgrad_bnsum(dy, wt, dx, partial, res, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride,
-                              pad, Kp, tile, splits, nullptr, nullptr, nullptr, 0, nullptr, st);
+  return launch(plan_dgrad(dy, wt, dx, partial, res, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride,
+                           pad, Kp, tile, splits, nullptr, nullptr, nullptr, 0, nullptr, 1, nullptr,
+                           0, 0, nullptr, nullptr, 0, 0), st);
 }
 
 // dx = dgrad(dy) (+ res) that also adds the BN-backward sums of the layer
@@ -2026,30 +2100,9 @@ MDA_API int mda_conv_dgrad_res(const void* dy, const void* wt, void* dx, float* 
 // mean / rstd / scale / shift, bn_act its activation, region a fresh zeroed
 // BnRegion for Cin channels.  Requires splits == 1 (the split-K combine has
 // no reduction epilogue) and Cin % 8 == 0.
-MDA_API int mda_conv_dgrad_bnsum(const void* dy, const void* wt, void* dx, float* partial,
-                                 const void* res, int64_t N, int64_t H, int64_t W, int64_t Cin,
-                                 int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
-                                 int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
-                                 int64_t splits, const void* bn_y, const void* bn_res,
-                                 const float* bn_stats, int64_t bn_act, void* region,
-                                 hipStream_t st) {
-  return mda_conv_dgrad_bnsum_g(dy, wt, dx, partial, res, N, H, W, Cin, Ho, Wo, Cout, KH, KW,
-                                stride, pad, Kp, tile, splits, bn_y, bn_res, bn_stats, bn_act,
-                                region, 1, nullptr, 0, 0, st);
-}
-
-// Grouped dgrad (groups > 1): dx[.., g*Cin/G + ci] sums only group g's output
+// Grouped (groups > 1): dx[.., g*Cin/G + ci] sums only group g's output
 // channels; wt packed [Cin][KpT] with k = tap * (Cout/G) + co_in_group
 // (mda_pack_conv_weights_gc).  The GEMM runs with group-aligned tiles.
-static int conv_dgrad_impl(const void* dy, const void* wt, void* dx, float* partial,
-                           const void* res, int64_t N, int64_t H, int64_t W, int64_t Cin,
-                           int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
-                           int64_t stride, int64_t pad, int64_t Kp, int64_t tile, int64_t splits,
-                           const void* bn_y, const void* bn_res, const float* bn_stats,
-                           int64_t bn_act, void* region, int64_t groups, const float* bn_vres,
-                           int64_t bn_mh, int64_t bn_rstride, const void* x2, const void* w2,
-                           int64_t cin2, int64_t kp2, hipStream_t st);
-
 MDA_API int mda_conv_dgrad_bnsum_g(const void* dy, const void* wt, void* dx, float* partial,
                                    const void* res, int64_t N, int64_t H, int64_t W, int64_t Cin,
                                    int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
@@ -2058,9 +2111,9 @@ MDA_API int mda_conv_dgrad_bnsum_g(const void* dy, const void* wt, void* dx, flo
                                    const float* bn_stats, int64_t bn_act, void* region,
                                    int64_t groups, const float* bn_vres, int64_t bn_mh,
                                    int64_t bn_rstride, hipStream_t st) {
-  return conv_dgrad_impl(dy, wt, dx, partial, res, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride,
-                         pad, Kp, tile, splits, bn_y, bn_res, bn_stats, bn_act, region, groups,
-                         bn_vres, bn_mh, bn_rstride, nullptr, nullptr, 0, 0, st);
+  return launch(plan_dgrad(dy, wt, dx, partial, res, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride,
+                           pad, Kp, tile, splits, bn_y, bn_res, bn_stats, bn_act, region, groups,
+                           bn_vres, bn_mh, bn_rstride, nullptr, nullptr, 0, 0), st);
 }
 
 // mda_conv_dgrad_bnsum_g of a stride-s conv with a 1 x 1 / stride-s / pad-0
@@ -2077,76 +2130,9 @@ MDA_API int mda_conv_dgrad_bnsum2(const void* dy, const void* wt, void* dx, int6
                                   int64_t bn_act, void* region, const float* bn_vres,
                                   const void* dy2, const void* wt2, int64_t cin2, int64_t kp2,
                                   hipStream_t st) {
-  if (dy2 == nullptr || wt2 == nullptr || cin2 <= 0 || cin2 % BK || kp2 < cin2 || kp2 % BK)
-    return MDA_NOT_SERVED;
-  int64_t tile = 0, splits = 0;
-  mda_conv_plan(N * H * W, Cin, Kp, &tile, &splits);
-  if (splits != 1) return MDA_NOT_SERVED;
-  return conv_dgrad_impl(dy, wt, dx, nullptr, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride,
-                         pad, Kp, tile, splits, bn_y, bn_res, bn_stats, bn_act, region, 1, bn_vres,
-                         0, 0, dy2, wt2, cin2, kp2, st);
-}
-
-static int conv_dgrad_impl(const void* dy, const void* wt, void* dx, float* partial,
-                           const void* res, int64_t N, int64_t H, int64_t W, int64_t Cin,
-                           int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
-                           int64_t stride, int64_t pad, int64_t Kp, int64_t tile, int64_t splits,
-                           const void* bn_y, const void* bn_res, const float* bn_stats,
-                           int64_t bn_act, void* region, int64_t groups, const float* bn_vres,
-                           int64_t bn_mh, int64_t bn_rstride, const void* x2, const void* w2,
-                           int64_t cin2, int64_t kp2, hipStream_t st) {
-  if (Cout % 8 || groups < 1 || Cin % groups || Cout % groups) return (int)hipErrorInvalidValue;
-  if (region != nullptr && (splits != 1 || Cin % 8 || Cin > SLOT_CMAX || bn_y == nullptr ||
-                            bn_stats == nullptr))
-    return (int)hipErrorInvalidValue;
-  // two stacked sets: dx rows [mh, 2 mh) are set 1 (N holds both sets' images)
-  if (bn_mh != 0 && (region == nullptr || bn_mh * 2 != N * H * W || bn_rstride <= 0))
-    return (int)hipErrorInvalidValue;
-  ConvParams p{};
-  p.bnb_mh = (int)bn_mh;
-  p.bnb_rstride = bn_rstride;
-  p.bnb_y = (const bf16_t*)bn_y;
-  p.bnb_res = (const bf16_t*)bn_res;
-  p.bnb_stats = bn_stats;
-  p.bnb_slot = (BnRegion*)region;
-  p.bnb_act = (int)bn_act;
-  p.bnb_vres = bn_res != nullptr ? bn_vres : nullptr;
-  p.x2 = (const bf16_t*)x2;
-  p.w2 = (const bf16_t*)w2;
-  p.cin2 = (int)cin2;
-  p.kp2 = (int)kp2;
-  p.cls2 = -1;
-  p.sh2 = 0;
-  p.x = (const bf16_t*)dy; p.w = (const bf16_t*)wt; p.scale = nullptr; p.bias = nullptr;
-  p.res = (const bf16_t*)res; p.y = (bf16_t*)dx; p.preact = nullptr; p.partial = partial;
-  // GEMM view: rows = dx pixels, cols = Cin, k = (tap, co); "input" image = dy
-  p.N = N; p.H = Ho; p.W = Wo; p.Cin = Cout / groups; p.Ho = H; p.Wo = W; p.Cout = Cin; p.KH = KH;
-  p.KW = KW; p.stride = stride; p.pad = pad; p.K = KH * KW * p.Cin; p.Kp = Kp; p.M = N * H * W;
-  p.act = 0;
-  p.ldx = (int)Cout;
-  p.cout_g = (int)(Cin / groups);
-  int mode = (p.Cin % BK == 0) ? LOAD_DGRAD_FAST : LOAD_DGRAD_VEC8;
-  p.par = 0;
-  p.zsplits = 1;
-  p.stats_part = nullptr;
-  p.stats_slot = nullptr;
-  p.stamps = g_stamps;
-  // strided dgrad: one GEMM per output-parity class with only its taps
-  if (stride > 1 && mode == LOAD_DGRAD_FAST && use_glds() && use_par_dgrad() && groups == 1)
-    p.par = (int)stride;
-  if (x2 != nullptr) {
-    if (p.par <= 1 || groups != 1 || bn_mh != 0) return MDA_NOT_SERVED;
-    // the 1 x 1 / stride-s / pad-0 conv samples dx pixels (s i, s j): parity
-    // class (pad mod s, pad mod s), whose dy pixel minus pad / s is (i, j)
-    const int ph = (int)(pad % stride);
-    p.cls2 = ph * (int)stride + ph;
-    p.sh2 = (int)(pad / stride);
-    if (tile == 0 || splits == 0) mda_conv_plan(p.M, p.Cout, p.Kp, &tile, &splits);
-    if (splits != 1) return MDA_NOT_SERVED;
-  }
-  if (groups > 1 && (p.Cin % 8 || p.cout_g % 8)) return (int)hipErrorInvalidValue;
-  // stride-1 3x3 pad-1 dgrad is a "same" conv of dy with the mirrored taps
-  return dispatch(p, mode, tile, splits, st, (groups == 1 && halo_eligible(p)) ? 2 : 0);
+  return launch(plan_dgrad_pair(dy, wt, dx, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp,
+                                bn_y, bn_res, bn_stats, bn_act, region, bn_vres, dy2, wt2, cin2,
+                                kp2), st);
 }
 
 // Training conv + BN statistics, two launches: the conv writes the raw bf16
@@ -2175,36 +2161,15 @@ MDA_API int mda_conv_fwd_bnstats(const void* x, const void* w, void* y, float* p
                                  const float* beta, float* running_mean, float* running_var,
                                  float* mean, float* rstd, float* scale, float* shift,
                                  float momentum, float eps, int64_t* nbt, hipStream_t st) {
-  ConvParams p{};
-  p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = nullptr; p.bias = nullptr;
-  p.res = nullptr; p.y = (bf16_t*)y; p.preact = nullptr; p.partial = partial;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.KH = KH;
-  p.KW = KW; p.stride = stride; p.pad = pad; p.K = KH * KW * Cin; p.Kp = Kp; p.M = N * Ho * Wo;
-  p.act = 0;
-  p.par = 0;
-  p.zsplits = 1;
-  p.stats_part = nullptr;
-  p.stats_slot = nullptr;
-  p.stamps = g_stamps;
-  if (Cout % 8 || Cout > 2048) return (int)hipErrorInvalidValue;
-  int mode = (Cin % BK == 0) ? LOAD_FAST : (Cin % 8 == 0 ? LOAD_VEC8 : LOAD_SCALAR);
-  if (tile == 0 || splits == 0) mda_conv_plan(p.M, p.Cout, p.Kp, &tile, &splits);
-  const int halo = halo_eligible(p) ? 1 : 0;
-  // M-blocks of the launch that will run (see dispatch)
-  int64_t nblk;
-  if (halo && !(!((Cin / BK) == 1 && splits == 1 && use_halo1()) &&
-                     p.himgs * (p.hrows + 2) * (p.W + 2) > HALO_PROWS))
-    nblk = (p.M + p.hpb - 1) / p.hpb;
-  else
-    nblk = (p.M + tile / 1000 - 1) / (tile / 1000);
-  const bool fused = splits == 1 && nblk * 2 * Cout <= bn_partial_cap;
-  if (fused) p.stats_part = bn_partial;
-  int rc = dispatch(p, mode, tile, splits, st, halo);
+  bool fused;
+  const ConvCall c = plan_fwd_bnstats(x, w, y, partial, bn_partial, bn_partial_cap, N, H, W, Cin,
+                                      Ho, Wo, Cout, KH, KW, stride, pad, Kp, tile, splits, &fused);
+  const int rc = launch(c, st);
   if (rc) return rc;
   if (fused)
-    return mda_bn_finalize(bn_partial, nblk, p.M, Cout, gamma, beta, running_mean, running_var,
-                           mean, rstd, scale, shift, momentum, eps, nbt, st);
-  return mda_bn_stats2(y, p.M, Cout, bn_partial, gamma, beta, running_mean, running_var, mean,
+    return mda_bn_finalize(bn_partial, c.r.grid.x, c.p.M, Cout, gamma, beta, running_mean,
+                           running_var, mean, rstd, scale, shift, momentum, eps, nbt, st);
+  return mda_bn_stats2(y, c.p.M, Cout, bn_partial, gamma, beta, running_mean, running_var, mean,
                        rstd, scale, shift, momentum, eps, nbt, st);
 }
 
@@ -2213,55 +2178,63 @@ MDA_API int mda_conv_fwd_bnstats(const void* x, const void* w, void* y, float* p
 // whose prologue finalizes them (2 launches per conv + BN instead of 3).
 // Split-K convs (sums only final after the combine) run the conv, then the
 // standalone statistics pass into the same slot.
+// Grouped (groups > 1, Cin/G and Cout/G multiples of 8): w packed [Cout][Kp]
+// over the Cin/G channels of each output channel's group (the OIHW weight of
+// a grouped conv packed as if dense, mda_pack_conv_weights with Cin/G).
 extern "C" int mda_bn_stats_acc(const void* y, int64_t M, int64_t C, void* region, hipStream_t st);
 
 MDA_API int mda_conv_fwd_bnacc_g(const void* x, const void* w, void* y, float* partial,
                                  void* region, int64_t N, int64_t H, int64_t W, int64_t Cin,
                                  int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
                                  int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
-                                 int64_t splits, int64_t groups, hipStream_t st);
-
-MDA_API int mda_conv_fwd_bnacc(const void* x, const void* w, void* y, float* partial, void* region,
-                               int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Ho,
-                               int64_t Wo, int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
-                               int64_t pad, int64_t Kp, int64_t tile, int64_t splits,
-                               hipStream_t st) {
-  return mda_conv_fwd_bnacc_g(x, w, y, partial, region, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride,
-                              pad, Kp, tile, splits, 1, st);
-}
-
-// Grouped (groups > 1, Cin/G and Cout/G multiples of 8): w packed [Cout][Kp]
-// over the Cin/G channels of each output channel's group (the OIHW weight of
-// a grouped conv packed as if dense, mda_pack_conv_weights with Cin/G).
-MDA_API int mda_conv_fwd_bnacc_g(const void* x, const void* w, void* y, float* partial,
-                                 void* region, int64_t N, int64_t H, int64_t W, int64_t Cin,
-                                 int64_t Ho, int64_t Wo, int64_t Cout, int64_t KH, int64_t KW,
-                                 int64_t stride, int64_t pad, int64_t Kp, int64_t tile,
                                  int64_t splits, int64_t groups, hipStream_t st) {
-  if (groups < 1 || Cin % groups || Cout % groups) return (int)hipErrorInvalidValue;
-  ConvParams p{};
-  p.ldx = (int)Cin;
-  p.cout_g = (int)(Cout / groups);
-  Cin /= groups;
-  p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = nullptr; p.bias = nullptr;
-  p.res = nullptr; p.y = (bf16_t*)y; p.preact = nullptr; p.partial = partial;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.KH = KH;
-  p.KW = KW; p.stride = stride; p.pad = pad; p.K = KH * KW * Cin; p.Kp = Kp; p.M = N * Ho * Wo;
-  p.act = 0;
-  p.par = 0;
-  p.zsplits = 1;
-  p.stats_part = nullptr;
-  p.stats_slot = nullptr;
-  p.stamps = g_stamps;
-  if (Cout % 8 || Cout > SLOT_CMAX) return (int)hipErrorInvalidValue;
-  int mode = (Cin % BK == 0) ? LOAD_FAST : (Cin % 8 == 0 ? LOAD_VEC8 : LOAD_SCALAR);
-  if (groups > 1 && mode == LOAD_SCALAR) return (int)hipErrorInvalidValue;
-  if (tile == 0 || splits == 0) mda_conv_plan(p.M, p.Cout, p.Kp, &tile, &splits);
-  const int halo = (groups == 1 && halo_eligible(p)) ? 1 : 0;
-  if (splits == 1) p.stats_slot = (BnRegion*)region;
-  int rc = dispatch(p, mode, tile, splits, st, halo);
-  if (rc || splits == 1) return rc;
-  return mda_bn_stats_acc(y, p.M, Cout, region, st);
+  const ConvCall c = plan_fwd_bnacc(x, w, y, partial, region, N, H, W, Cin, Ho, Wo, Cout, KH, KW,
+                                    stride, pad, Kp, tile, splits, groups);
+  const int rc = launch(c, st);
+  if (rc || c.r.splits == 1) return rc;  // unsplit: the epilogue added the statistics
+  return mda_bn_stats_acc(y, c.p.M, Cout, region, st);
 }
 
-
+// Dry route query: which kernel, tile and grid would run op (0 mda_conv_fwd,
+// 1 mda_conv_fwd_bnstats, 2 mda_conv_fwd_bnacc_g, 3 mda_conv_dgrad_bnsum_g,
+// 4 mda_conv_dgrad_bnsum2) on this shape.  It runs the entry point's own
+// planner, with every workspace present and large enough, and launches
+// nothing; no GPU is needed.  groups applies to ops 2 and 3.  fused_pair: op 3,
+// nonzero = the BN-backward sums are fused in (a region is given); op 4, cin2
+// of the folded 1 x 1 conv (kp2 = cin2 rounded up to 64).  out: 15 int64 = the
+// entry point's status, stream1x1 offer, and for status 0: family (0 glds,
+// 1 reg, 2 halo, 3 halo1), bm, bn, load mode, ring, flip, grid x / y / z,
+// steps_per_split, splits, split-K combine blocks, and for op 1 the per-block
+// partial rows nblk.  Returns 0 unless op is unknown.
+MDA_API int mda_conv_route(int64_t op, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Ho,
+                           int64_t Wo, int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                           int64_t pad, int64_t Kp, int64_t groups, int64_t tile, int64_t splits,
+                           int64_t fused_pair, int64_t* out) {
+  static float buf[1];  // stands for every operand: the planners dereference none
+  float* const F = buf;
+  void* const D = buf;
+  void* const pair = fused_pair ? D : nullptr;
+  bool fused;
+  ConvCall c = refused((int)hipErrorInvalidValue);
+  if (op == 0 && groups == 1)
+    c = plan_fwd(D, D, D, F, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp, tile, splits);
+  else if (op == 1 && groups == 1)
+    c = plan_fwd_bnstats(D, D, D, F, F, INT64_MAX, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad,
+                         Kp, tile, splits, &fused);
+  else if (op == 2)
+    c = plan_fwd_bnacc(D, D, D, F, D, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp, tile,
+                       splits, groups);
+  else if (op == 3)
+    c = plan_dgrad(D, D, D, F, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp, tile,
+                   splits, pair, nullptr, (const float*)pair, 0, pair, groups, nullptr, 0, 0,
+                   nullptr, nullptr, 0, 0);
+  else if (op == 4 && groups == 1)
+    c = plan_dgrad_pair(D, D, D, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp, D, nullptr, F,
+                        0, D, nullptr, pair, pair, fused_pair, (fused_pair + BK - 1) / BK * BK);
+  const ConvRoute& r = c.r;
+  const int64_t route[15] = {r.rc, r.stream1x1, r.family, r.bm, r.bn, r.mode, r.ring, r.flip,
+                             r.grid.x, r.grid.y, r.grid.z, r.steps_per_split, r.splits,
+                             r.combine_blocks, op == 1 ? r.grid.x : 0};
+  for (int i = 0; i < 15; ++i) out[i] = (i < 2 || r.rc == 0) ? route[i] : 0;
+  return op < 0 || op > 4 ? (int)hipErrorInvalidValue : 0;
+}

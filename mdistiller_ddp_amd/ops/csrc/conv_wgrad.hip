@@ -1144,14 +1144,8 @@ MDA_API int mda_pack_tiles(int64_t Cout, int64_t Cin, int64_t KH, int64_t KW, in
 // 3x3 layers and the scalar stem gather.  MDA_WG_TILE=<code> forces a tile,
 // MDA_WG_GLDS=0 the register-staged kernel.
 static int wg_tile(int64_t M, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW, int64_t Kp) {
-  static const int forced = [] {
-    const char* e = getenv("MDA_WG_TILE");
-    return e ? atoi(e) : -1;
-  }();
-  static const bool glds = [] {
-    const char* e = getenv("MDA_WG_GLDS");
-    return !(e && e[0] == '0');
-  }();
+  static const int forced = (int)mda_env_int("MDA_WG_TILE", -1);
+  static const bool glds = mda_env_flag("MDA_WG_GLDS", true);
   if (Cin % 8 || !glds) return 0;
   if (forced == 0 || forced == 64064 || forced == 64128 || forced == 128064 || forced == 128128) return forced;
   if (KH * KW == 1) return (Cout >= 128 && Kp >= 128) ? 128128 : 64064;
@@ -1176,10 +1170,7 @@ static bool wg_halo_geom(int64_t H, int64_t W, int64_t* rh, int64_t* img) {
 
 static bool wg_halo_ok(int64_t M, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW, int64_t H,
                        int64_t W, int64_t stride, int64_t pad) {
-  static const bool on = [] {
-    const char* e = getenv("MDA_WG_HALO");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = mda_env_flag("MDA_WG_HALO", true);
   int64_t rh, img;
   return on && KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cin % 64 == 0 && Cout % 64 == 0 &&
          M % 64 == 0 && wg_halo_geom(H, W, &rh, &img);
@@ -1192,10 +1183,7 @@ static bool wg_halo_ok(int64_t M, int64_t Cout, int64_t Cin, int64_t KH, int64_t
 // flagship 0.7707 -> 0.7605 ms/step (0.7678 -> 0.7614 in a second set); the
 // student alone 0.6130 -> 0.6208 (profiles/r6_ab.md).  MDA_WGH_BLOCKS: A/B.
 static int64_t wg_halo_splits(int64_t M, int64_t Cout, int64_t Cin) {
-  static const int64_t target = [] {
-    const char* e = getenv("MDA_WGH_BLOCKS");
-    return e ? (int64_t)atoi(e) : (int64_t)64;
-  }();
+  static const int64_t target = (int)mda_env_int("MDA_WGH_BLOCKS", 64);
   const int64_t tiles = (Cout / 64) * (Cin / 64), stages = M / 64;
   int64_t sp = (target + tiles - 1) / tiles;
   sp = std::min<int64_t>(sp, std::max<int64_t>(1, stages / 2));
@@ -1220,10 +1208,8 @@ MDA_API int mda_wgrad_plan(int64_t M, int64_t Cout, int64_t Cin, int64_t KH, int
     // one round of blocks over the CU slots (LDS-limited blocks per CU), each
     // split >= 8 stages of 64 pixels, at most 128 partial sets
     const int64_t occ = tile == 128128 ? 1 : (tile == 64064 ? 3 : 2);
-    static const int64_t slots = [] {  // CU slots to fill (MDA_WG_SLOTS, A/B)
-      const char* e = getenv("MDA_WG_SLOTS");
-      return e ? (int64_t)atoi(e) : (int64_t)256;
-    }();
+    // CU slots to fill (MDA_WG_SLOTS, A/B)
+    static const int64_t slots = (int)mda_env_int("MDA_WG_SLOTS", 256);
     sp = (slots * occ + tiles - 1) / tiles;
     sp = std::min<int64_t>(sp, std::max<int64_t>(1, M / (8 * TM)));
     sp = std::max<int64_t>(1, std::min<int64_t>(sp, 128));

@@ -440,11 +440,8 @@ dw_wgrad_partial_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__
 // 64 KB: R50->MV1 6.34 / 6.44 / 6.63 ms, VGG13->MV2 2.62 / 2.61 / 2.61,
 // register kernels 6.41 / 2.70 -- profiles/r4_dw_fusion_ab.md)
 inline int64_t dwt_budget() {
-  static const int64_t b = [] {
-    const char* e = getenv("MDA_DW_TILE_KB");
-    const int64_t k = e ? atoll(e) : 24;
-    return (k >= 8 && k <= 150 ? k : 24) * 1024;
-  }();
+  static const int64_t k = mda_env_int("MDA_DW_TILE_KB", 24);
+  static const int64_t b = (k >= 8 && k <= 150 ? k : 24) * 1024;
   return b;
 }
 
@@ -609,10 +606,7 @@ __global__ void __launch_bounds__(256) dw_dgrad_tile_kernel(const DwParams p, in
 // block's LDS fits dwt_budget(); false = not served (the register kernels run).
 inline bool dw_tile_plan(int H, int W, int C, int Ho, int Wo, int S, int pad, bool with_dy, int& tr,
                          int& cc) {
-  static const bool on = [] {
-    const char* e = getenv("MDA_DW_TILE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = mda_env_flag("MDA_DW_TILE", true);
   cc = C % 64 == 0 ? 64 : C % 32 == 0 ? 32 : C % 16 == 0 ? 16 : 8;  // channels per block
   if (!on || pad != 1 || C % cc || (S != 1 && S != 2)) return false;
   for (int t = Ho < 16 ? Ho : 16; t >= 1; --t) {
@@ -681,11 +675,8 @@ __global__ void dw_pack_kernel(const float* __restrict__ w, const float* __restr
 // ~150 (3 waves); R50->MV1 6.55 -> 6.40 ms, VGG13->MV2 2.77 -> 2.68
 // (profiles/r4_dw_fusion_ab.md)
 inline int vwidth(int C) {
-  static const int vmax = [] {
-    const char* e = getenv("MDA_DW_VMAX");
-    const int v = e ? atoi(e) : 4;
-    return (v == 1 || v == 2 || v == 8) ? v : 4;
-  }();
+  static const int knob = (int)mda_env_int("MDA_DW_VMAX", 4);
+  static const int vmax = (knob == 1 || knob == 2 || knob == 8) ? knob : 4;
   const int v = (C % 8 == 0) ? 8 : (C % 4 == 0) ? 4 : (C % 2 == 0) ? 2 : 1;
   return v < vmax ? v : vmax;
 }
@@ -816,10 +807,7 @@ MDA_API int mda_dw_wgrad_blocks(int64_t N, int64_t Ho, int64_t Wo, int64_t C, in
   // lanes' independent load batches hide the memory latency (the finalize
   // reads the nblk partials in parallel)
   // (A/B, profiles/r2_misc_ab.md: 1 for CIFAR-size maps, 2 for 112^2 ImageNet ones)
-  static const int64_t forced = [] {
-    const char* e = getenv("MDA_DW_WG_IPL");
-    return e ? (int64_t)atoi(e) : (int64_t)0;
-  }();
+  static const int64_t forced = (int)mda_env_int("MDA_DW_WG_IPL", 0);
   const int64_t ipl = forced > 0 ? forced : (N * Ho * ((Wo + OWT - 1) / OWT) < 200000 ? 1 : 2);
   int64_t b = (items + PL * ipl - 1) / (PL * ipl);
   if (b > 1024) b = 1024;

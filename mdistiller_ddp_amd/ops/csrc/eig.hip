@@ -175,11 +175,8 @@ __global__ void __launch_bounds__(256) sym_eig_kernel(EigTable tab, int sweeps) 
 static int eig_threads() {
   // block size (64 / 128 / 256; MDA_EIG_THREADS): the Jacobi steps are
   // latency bound, fewer waves make each step's barriers cheaper
-  static const int threads = [] {
-    const char* e = getenv("MDA_EIG_THREADS");
-    const int t = e ? atoi(e) : 256;
-    return (t == 64 || t == 128) ? t : 256;
-  }();
+  static const int t = (int)mda_env_int("MDA_EIG_THREADS", 256);
+  static const int threads = (t == 64 || t == 128) ? t : 256;
   return threads;
 }
 

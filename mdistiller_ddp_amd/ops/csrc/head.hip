@@ -519,10 +519,7 @@ MDA_API int mda_pool_fc_bwd_bn(int64_t dt, const void* dl, const void* dpooled, 
   const size_t lds = (size_t)((N > J ? N : J) + C + 2 * pp * C) * sizeof(float);
   if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
   // images split over ksplit blocks (>= 16 pixels each) on the vector path
-  static const int kmax = [] {
-    const char* e = getenv("MDA_HEAD_KSPLIT");
-    return e ? atoi(e) : 4;
-  }();
+  static const int kmax = (int)mda_env_int("MDA_HEAD_KSPLIT", 4);
   int ksplit = 1;
   if (dt != DT_F32 && pp > 0 && kmax > 1)
     for (int k = kmax; k > 1; k >>= 1)

@@ -339,7 +339,7 @@ class BnLink:
 
     The consumer's dgrad produces exactly this layer's output gradient, so its
     epilogue can also add the layer's backward channel sums (sum dz,
-    sum dz*xhat) into a fresh region (``mda_conv_dgrad_bnsum``, :meth:`arm`);
+    sum dz*xhat) into a fresh region (``mda_conv_dgrad_bnsum_g``, :meth:`arm`);
     the layer's backward then runs ONE streaming pass on them
     (``mda_bn_bwd_apply_reg``) instead of a reduction + grid barrier + apply.
     The sums are used only if the gradient the layer receives IS that dgrad

@@ -51,8 +51,8 @@ def main():
 
     def run():
         if a.op == "bnsum":
-            _ext.call("mda_conv_dgrad_bnsum", dy, wt, dx, part, None, N, H, H, Cin, Ho, Ho, Cout, k, k,
-                      s, p, KpT, tile, splits, bn_y, bn_res, stats, 1, region)
+            _ext.call("mda_conv_dgrad_bnsum_g", dy, wt, dx, part, None, N, H, H, Cin, Ho, Ho, Cout, k, k,
+                      s, p, KpT, tile, splits, bn_y, bn_res, stats, 1, region, 1, None, 0, 0)
         elif a.op == "fold":
             _ext.call("mda_conv_dgrad_bnsum2", dy, wt, dx, N, H, H, Cin, Ho, Ho, Cout, k, k, s, p, KpT,
                       bn_y, bn_res, stats, 1, region, None, dy2, wt2, Cout, kp2)

@@ -1,5 +1,5 @@
 """BN-backward sums in the consumer conv's dgrad epilogue (ops/hip_train.py
-BnLink, conv_igemm.hip mda_conv_dgrad_bnsum, bn.hip mda_bn_bwd_apply_reg):
+BnLink, conv_igemm.hip mda_conv_dgrad_bnsum_g, bn.hip mda_bn_bwd_apply_reg):
 a training conv+BN+act layer whose output feeds the next native conv gets its
 sum dz / sum dz*xhat from that conv's dgrad and runs one streaming backward
 pass.  Checked against the same native layers with the link off (the
